@@ -7,7 +7,14 @@ rank per GPU over RCCL (weak scaling: each rank runs an independent stream
 shard, matching the engine's stream-per-GPU sharding model).
 
   python bench.py --gpus N --steps K --warmup W [--model mlp|bert]
-                  [--batch-size 8192]
+                  [--batch-size 8192] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step returned, one
+DIR/<column>.npy per output column, so two builds can be compared output for
+output (the generator and the weights are seeded: same arguments, same
+inputs). --full is where everything beyond the headline figure belongs;
+today the benchmark measures nothing else, so it adds nothing.
 
 One step = one batch of --batch-size rows through the full pipeline
 (synthetic generator data, random-init weights; bf16 inference compute).
@@ -20,6 +27,7 @@ import os
 import statistics
 import time
 
+import numpy as np
 import torch
 
 
@@ -177,17 +185,20 @@ async def run_steps(gen, pipeline, n_steps, workers=1):
     """Process n_steps batches. workers>1 pipelines steps concurrently the
     way the engine's thread_num processor workers do (stream.py), overlapping
     host dispatch of step k+1 with device execution of step k; per-step
-    latency (p50) is still measured per batch with a sync."""
+    latency (p50) is still measured per batch with a sync. Also returns the
+    batches the LAST step produced (views into the step's static buffers —
+    valid until the next read)."""
     rows = 0
     times = []
+    last = []
 
     loop = asyncio.get_running_loop()
 
     async def one_step():
-        nonlocal rows
+        nonlocal rows, last
         t0 = time.perf_counter()
         batch, ack = await gen.read()
-        outs = await pipeline.process(batch)
+        outs = last = await pipeline.process(batch)
         for b in outs:
             rows += b.num_rows
         if batch.device.type == "cuda":
@@ -208,7 +219,7 @@ async def run_steps(gen, pipeline, n_steps, workers=1):
     if workers <= 1:
         for _ in range(n_steps):
             await one_step()
-        return rows, times
+        return rows, times, last
 
     sem = asyncio.Semaphore(workers)
 
@@ -217,7 +228,42 @@ async def run_steps(gen, pipeline, n_steps, workers=1):
             await one_step()
 
     await asyncio.gather(*[guarded() for _ in range(n_steps)])
-    return rows, times
+    return rows, times, last
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # ceiling for everything --dump-outputs writes
+
+
+def dump_outputs(outs, out_dir):
+    """Write the columns of the last step's output batches as
+    out_dir/<column>.npy — float32, or float64 where float32 would lose
+    bits (int64 / float64 columns). Binary columns are written as their
+    byte and offset arrays. An array over its share of the 64 MB budget is
+    cut to a fixed, seeded sample of its elements (sorted indices, so order
+    is kept)."""
+    arrays = {}
+    for i, b in enumerate(outs):
+        pre = "" if len(outs) == 1 else f"out{i}_"
+        for name, col in b.columns.items():
+            if col.kind == "binary":
+                arrays[f"{pre}{name}.bytes"] = col.data
+                arrays[f"{pre}{name}.offsets"] = col.offsets
+            else:
+                arrays[pre + name] = col.data
+    os.makedirs(out_dir, exist_ok=True)
+    if not arrays:
+        return
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        wide = t.dtype in (torch.int64, torch.float64)
+        t = t.detach().reshape(-1)
+        cap = share // (8 if wide else 4) - 32  # leave room for the header
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(
+                t.numel(), size=cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -234,6 +280,12 @@ def main():
                    help="concurrent in-flight steps (engine thread_num analog)")
     p.add_argument("--no-stepgraph", action="store_true",
                    help="disable the whole-step hipGraph for --model mlp")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "output columns as DIR/<column>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the benchmark measures beyond "
+                        "the headline figure (nothing today)")
     args = p.parse_args()
 
     args.rank = int(os.environ.get("RANK", 0))
@@ -266,13 +318,16 @@ def main():
     if device.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rows, times = loop.run_until_complete(
+    rows, times, last = loop.run_until_complete(
         run_steps(gen, pipeline, args.steps, args.workers))
     if device.type == "cuda":
         torch.cuda.synchronize()
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and args.rank == 0:
+        dump_outputs(last, args.dump_outputs)
 
     # aggregate across ranks: MAX elapsed, SUM rows
     if dist:

@@ -197,18 +197,32 @@ streams:
 """ % tmp_path)
 
     world = 2
+    # init_from_env picks RCCL and device LOCAL_RANK whenever a GPU is
+    # visible. With fewer GPUs than ranks, rank 1 has no device: it dies and
+    # rank 0 waits for it forever. There the ranks run GPU-less, over gloo
+    # like the rest of this module — the CLI path under test is the same.
+    hide_gpus = 0 < torch.cuda.device_count() < world
     procs = []
-    for rank in range(world):
-        env = dict(os.environ)
-        env.update({
-            "RANK": str(rank), "LOCAL_RANK": str(rank),
-            "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
-            "MASTER_PORT": "29541",
-        })
-        procs.append(subprocess.Popen(
-            [sys.executable, "-m", "arkflow_amd", "--config", str(cfg)],
-            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
-    outs = [p.communicate(timeout=150) for p in procs]
+    try:
+        for rank in range(world):
+            env = dict(os.environ)
+            env.update({
+                "RANK": str(rank), "LOCAL_RANK": str(rank),
+                "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
+                "MASTER_PORT": "29541",
+            })
+            if hide_gpus:
+                env.update({"HIP_VISIBLE_DEVICES": "-1",
+                            "CUDA_VISIBLE_DEVICES": "-1"})
+            procs.append(subprocess.Popen(
+                [sys.executable, "-m", "arkflow_amd", "--config", str(cfg)],
+                env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
+        outs = [p.communicate(timeout=150) for p in procs]
+    finally:
+        for p in procs:  # never leave a rank behind waiting for its peer
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     for p, (so, se) in zip(procs, outs):
         assert p.returncode == 0, se.decode()[-2000:]
 
