@@ -366,27 +366,42 @@ std::tuple<torch::Tensor, torch::Tensor> join_inner_i64(torch::Tensor lk,
 }
 
 // ------------------------------------------------------------------ inference
-torch::Tensor gemm_bf16(torch::Tensor A, torch::Tensor Bt,
-                        c10::optional<torch::Tensor> bias, int64_t act) {
+// optional device vector → contiguous fp32 (undefined tensor when absent);
+// the kernels read it through a raw pointer, so device and length are checked
+torch::Tensor device_vec_f32(const c10::optional<torch::Tensor>& v,
+                             int64_t numel, const char* name) {
+  if (!v.has_value() || !v->defined()) return torch::Tensor();
+  TORCH_CHECK(v->is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(v->numel() == numel, name, " must have ", numel, " elements");
+  return v->scalar_type() == torch::kFloat32
+             ? v->contiguous()
+             : v->to(torch::kFloat32).contiguous();
+}
+
+// argument checks shared by gemm_bf16 and gemm_bf16_variant; returns the
+// fp32 bias (undefined when absent)
+torch::Tensor check_gemm_args(const torch::Tensor& A, const torch::Tensor& Bt,
+                              const c10::optional<torch::Tensor>& bias) {
   check_cuda(A, "A");
   check_cuda(Bt, "Bt");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 &&
                   Bt.scalar_type() == torch::kBFloat16,
               "gemm_bf16 requires bf16 inputs");
   TORCH_CHECK(A.dim() == 2 && Bt.dim() == 2, "A [M,K], Bt [N,K]");
-  int64_t M = A.size(0), K = A.size(1), N = Bt.size(0);
+  int64_t K = A.size(1);
   TORCH_CHECK(Bt.size(1) == K, "K mismatch");
   TORCH_CHECK(K % 32 == 0 && K >= 32, "K must be a multiple of 32");
+  return device_vec_f32(bias, Bt.size(0), "bias");
+}
+
+torch::Tensor gemm_bf16(torch::Tensor A, torch::Tensor Bt,
+                        c10::optional<torch::Tensor> bias, int64_t act) {
+  auto bias_f = check_gemm_args(A, Bt, bias);
+  int64_t M = A.size(0), K = A.size(1), N = Bt.size(0);
   auto C = torch::empty({M, N}, A.options());
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_f;
-  if (bias.has_value() && bias->defined()) {
-    bias_f = bias->scalar_type() == torch::kFloat32
-                 ? bias->contiguous()
-                 : bias->to(torch::kFloat32).contiguous();
-    TORCH_CHECK(bias_f.numel() == N, "bias must be [N]");
-    bias_ptr = bias_f.data_ptr<float>();
-  }
+  if (M == 0 || N == 0) return C;  // a zero-size grid is a launch error
+  const float* bias_ptr =
+      bias_f.defined() ? bias_f.data_ptr<float>() : nullptr;
   // measured dispatch (profiles/ r02/r06 GEMM tables): big square shapes →
   // 8-phase BM=256+swizzle; chip-filling mid shapes → 8-phase BM=128+swizzle;
   // everything else → the 128² single-buffer tile.
@@ -442,6 +457,7 @@ torch::Tensor gemv_bf16_f32(torch::Tensor x, torch::Tensor w, double bias) {
               w.scalar_type() == torch::kBFloat16, "bf16 required");
   TORCH_CHECK(x.dim() == 2 && w.numel() == x.size(1), "x [M,K], w [K]");
   auto out = torch::empty({x.size(0)}, x.options().dtype(torch::kFloat32));
+  if (x.size(0) == 0) return out;
   launch_gemv_bf16_f32(x.data_ptr(), w.data_ptr(), (float)bias, x.size(0),
                        (int)x.size(1), out.data_ptr<float>(), cur_stream());
   return out;
@@ -545,6 +561,9 @@ void featpack(std::vector<torch::Tensor> srcs, torch::Tensor out) {
               "out must be [n, kpad] bf16");
   int64_t n = out.size(0);
   int kpad = (int)out.size(1);
+  TORCH_CHECK((int64_t)srcs.size() <= out.size(1),
+              "out has fewer columns than sources");
+  if (n == 0) return;
   bool f64 = srcs[0].scalar_type() == torch::kFloat64;
   if (f64) {
     std::vector<const double*> ptrs;
@@ -571,16 +590,12 @@ torch::Tensor gemm_bf16_variant(torch::Tensor A, torch::Tensor Bt,
                                 c10::optional<torch::Tensor> bias,
                                 int64_t act, int64_t variant) {
   // variant: 0 = 128² tile, 1 = 8-phase linear LDS, 2 = 8-phase + swizzle
-  check_cuda(A, "A");
-  check_cuda(Bt, "Bt");
+  auto bias_f = check_gemm_args(A, Bt, bias);
   int64_t M = A.size(0), K = A.size(1), N = Bt.size(0);
   auto C = torch::empty({M, N}, A.options());
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_f;
-  if (bias.has_value() && bias->defined()) {
-    bias_f = bias->to(torch::kFloat32).contiguous();
-    bias_ptr = bias_f.data_ptr<float>();
-  }
+  if (M == 0 || N == 0) return C;
+  const float* bias_ptr =
+      bias_f.defined() ? bias_f.data_ptr<float>() : nullptr;
   if (variant == 0) {
     launch_gemm_bf16(A.data_ptr(), Bt.data_ptr(), bias_ptr, C.data_ptr(),
                      (int)M, (int)N, (int)K, (int)act, cur_stream());
@@ -639,18 +654,24 @@ torch::Tensor layernorm_bf16(torch::Tensor x, torch::Tensor gamma,
                              c10::optional<torch::Tensor> residual) {
   check_cuda(x, "x");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "x must be bf16");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., n], n > 0");
   int64_t n = x.size(-1);
   TORCH_CHECK(n % 8 == 0, "inner dim must be a multiple of 8");
   int64_t rows = x.numel() / n;
-  auto g = gamma.to(torch::kFloat32).contiguous();
-  auto b = beta.to(torch::kFloat32).contiguous();
+  TORCH_CHECK(gamma.defined() && beta.defined(), "gamma and beta required");
+  auto g = device_vec_f32(gamma, n, "gamma");
+  auto b = device_vec_f32(beta, n, "beta");
   auto out = torch::empty_like(x);
   const void* res_ptr = nullptr;
   if (residual.has_value() && residual->defined()) {
-    TORCH_CHECK(residual->is_contiguous() &&
-                residual->scalar_type() == torch::kBFloat16);
+    check_cuda(*residual, "residual");
+    TORCH_CHECK(residual->scalar_type() == torch::kBFloat16,
+                "residual must be bf16");
+    TORCH_CHECK(residual->sizes() == x.sizes(),
+                "residual must have x's shape");
     res_ptr = residual->data_ptr();
   }
+  if (rows == 0) return out;
   launch_layernorm_bf16(x.data_ptr(), res_ptr, g.data_ptr<float>(),
                         b.data_ptr<float>(), out.data_ptr(), nullptr, rows,
                         (int)n, (float)eps, cur_stream());
@@ -702,15 +723,14 @@ torch::Tensor bias_act_bf16(torch::Tensor x,
                             c10::optional<torch::Tensor> bias, int64_t act) {
   check_cuda(x, "x");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "x must be bf16");
+  auto out = torch::empty_like(x);
+  if (x.numel() == 0) return out;
+  TORCH_CHECK(x.dim() >= 1, "x must be [..., n]");
   int64_t n = x.size(-1);
   int64_t rows = x.numel() / n;
-  auto out = torch::empty_like(x);
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_f;
-  if (bias.has_value() && bias->defined()) {
-    bias_f = bias->to(torch::kFloat32).contiguous();
-    bias_ptr = bias_f.data_ptr<float>();
-  }
+  auto bias_f = device_vec_f32(bias, n, "bias");
+  const float* bias_ptr =
+      bias_f.defined() ? bias_f.data_ptr<float>() : nullptr;
   launch_bias_act_bf16(x.data_ptr(), bias_ptr, out.data_ptr(), rows, (int)n,
                        (int)act, cur_stream());
   return out;
@@ -723,6 +743,11 @@ torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   check_cuda(v, "v");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attention requires bf16");
   TORCH_CHECK(q.dim() == 4, "q must be [B,H,S,D]");
+  TORCH_CHECK(k.scalar_type() == q.scalar_type() &&
+                  v.scalar_type() == q.scalar_type(),
+              "k and v must match q's dtype");
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
+              "k and v must match q's shape");
   int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   auto out = torch::empty_like(q);
   int rc = launch_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),

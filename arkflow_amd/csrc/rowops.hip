@@ -20,6 +20,28 @@ DEV_INLINE float block_reduce_sum(float v, float* lds) {
   return total;
 }
 
+// All-lanes wave sum for the wave-per-row LayerNorm, whose two reductions
+// are serial (the mean feeds the squared deviations): four DPP row rotations
+// sum each 16-lane row in the VALU, then two xor shuffles combine the four
+// rows — 2 LDS-crossbar round trips instead of the 7 of shfl_down +
+// broadcast. Each step adds the same pair of values in both partner lanes, so
+// every lane ends with the same bits.
+template <int N>
+DEV_INLINE float row_ror_add(float v) {
+  int r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + N, 0xf,
+                                      0xf, false);  // row_ror:N
+  return v + __int_as_float(r);
+}
+DEV_INLINE float wave_allreduce_sum(float v) {
+  v = row_ror_add<8>(v);
+  v = row_ror_add<4>(v);
+  v = row_ror_add<2>(v);
+  v = row_ror_add<1>(v);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
 DEV_INLINE float block_reduce_max(float v, float* lds) {
   v = wave_reduce_max(v);
   const int wid = threadIdx.x >> 6;
@@ -50,7 +72,10 @@ void layernorm_bf16_kernel(const __bf16* __restrict__ x,
     const vbf16x8* xr = (const vbf16x8*)(x + row * n);
     const vbf16x8* rr =
         ADD_RESIDUAL ? (const vbf16x8*)(residual + row * n) : nullptr;
-    float sum = 0.f, sq = 0.f;
+    // two-pass variance: E[f^2] - mean^2 cancels catastrophically in fp32
+    // once |mean| >> stddev (x + residual rows); sum((f - mean)^2) is >= 0
+    // by construction. The second pass re-reads the row (L2-resident).
+    float sum = 0.f;
     for (int i = threadIdx.x; i < nv; i += ROW_THREADS) {
       vbf16x8 v = xr[i];
 #pragma unroll
@@ -58,11 +83,21 @@ void layernorm_bf16_kernel(const __bf16* __restrict__ x,
         float f = (float)v[j];
         if (ADD_RESIDUAL) f += (float)rr[i][j];
         sum += f;
-        sq += f * f;
       }
     }
     float mean = block_reduce_sum(sum, red) / n;
-    float var = block_reduce_sum(sq, red) / n - mean * mean;
+    float sq = 0.f;
+    for (int i = threadIdx.x; i < nv; i += ROW_THREADS) {
+      vbf16x8 v = xr[i];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float f = (float)v[j];
+        if (ADD_RESIDUAL) f += (float)rr[i][j];
+        float d = f - mean;
+        sq += d * d;
+      }
+    }
+    float var = block_reduce_sum(sq, red) / n;
     float rstd = rsqrtf(var + eps);
     vbf16x8* orow = (vbf16x8*)(out + row * n);
     vbf16x8* resrow =
@@ -103,6 +138,7 @@ void layernorm_bf16_wave_kernel(const __bf16* __restrict__ x,
   int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   int64_t wstride = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const bool cached = nv <= 2 * WAVE;  // lane holds <=2 vectors in regs
+  const float inv_n = 1.f / n;  // once per wave, off the per-row chain
   for (int64_t row = wave; row < rows; row += wstride) {
     const vbf16x8* xr = (const vbf16x8*)(x + row * n);
     const vbf16x8* rr =
@@ -111,6 +147,9 @@ void layernorm_bf16_wave_kernel(const __bf16* __restrict__ x,
     vbf16x8* resrow = (ADD_RESIDUAL && resid_out)
                           ? (vbf16x8*)(resid_out + row * n)
                           : nullptr;
+    // two-pass variance (see layernorm_bf16_kernel): mean first, then
+    // sum((f - mean)^2) from the register cache, or from a re-read of the
+    // row when it is streamed.
     float sum = 0.f, sq = 0.f;
     float c0[16];  // row cache: the (x+residual) floats, read-once
     if (cached) {
@@ -125,7 +164,6 @@ void layernorm_bf16_wave_kernel(const __bf16* __restrict__ x,
             if (ADD_RESIDUAL) f += (float)rr[i][j];
             c0[t * 8 + j] = f;
             sum += f;
-            sq += f * f;
           }
         }
       }
@@ -137,16 +175,34 @@ void layernorm_bf16_wave_kernel(const __bf16* __restrict__ x,
           float f = (float)v[j];
           if (ADD_RESIDUAL) f += (float)rr[i][j];
           sum += f;
-          sq += f * f;
         }
       }
     }
-    sum = wave_reduce_sum(sum);
-    sq = wave_reduce_sum(sq);
-    sum = __shfl(sum, 0, 64);  // broadcast (reduce leaves lane 0 complete)
-    sq = __shfl(sq, 0, 64);
-    float mean = sum / n;
-    float var = sq / n - mean * mean;
+    float mean = wave_allreduce_sum(sum) * inv_n;
+    if (cached) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (lane + t * WAVE < nv) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float d = c0[t * 8 + j] - mean;
+            sq += d * d;
+          }
+        }
+      }
+    } else {
+      for (int i = lane; i < nv; i += WAVE) {
+        vbf16x8 v = xr[i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float f = (float)v[j];
+          if (ADD_RESIDUAL) f += (float)rr[i][j];
+          float d = f - mean;
+          sq += d * d;
+        }
+      }
+    }
+    float var = wave_allreduce_sum(sq) * inv_n;
     float rstd = rsqrtf(var + eps);
     if (cached) {
 #pragma unroll

@@ -316,7 +316,14 @@ __global__ void featpack64_kernel(PackSpec64 spec, int64_t n,
   for (; i < n; i += stride) {
     __bf16* row = out + i * spec.kpad;
 #pragma unroll 4
-    for (int f = 0; f < spec.nf; ++f) row[f] = (__bf16)(float)spec.src[f][i];
+    for (int f = 0; f < spec.nf; ++f) {
+      // round to fp32 first, like the eager path's x.float().to(bf16): the
+      // empty asm keeps the compiler from fusing the two casts into one
+      // f64→bf16 rounding, which differs next to a bf16 tie
+      float v = (float)spec.src[f][i];
+      asm volatile("" : "+v"(v));
+      row[f] = (__bf16)v;
+    }
     for (int f = spec.nf; f < spec.kpad; ++f) row[f] = (__bf16)0.f;
   }
 }
