@@ -9,6 +9,8 @@
 #include <tuple>
 #include <vector>
 
+#include "gemm_api.h"  // GemmVariant, GemmArgs, launch_gemm_bf16
+
 // ---- extern kernel launchers (defined in the .hip TUs) ----------------------
 extern "C" {
 int filter_grid(int64_t n);
@@ -45,12 +47,6 @@ void launch_join_probe_emit(const int64_t*, int64_t, const int64_t*,
                             const int32_t*, const int32_t*, const int64_t*,
                             uint32_t, const int32_t*, int64_t*, int64_t*,
                             hipStream_t);
-void launch_gemm_bf16(const void*, const void*, const float*, void*, int, int,
-                      int, int, hipStream_t);
-int launch_gemm_bf16_8p(const void*, const void*, const float*, void*, int,
-                        int, int, int, int, hipStream_t);
-int launch_gemm_bf16_2p(const void*, const void*, const float*, void*, int,
-                        int, int, int, hipStream_t);
 void launch_layernorm_bf16(const void*, const void*, const float*,
                            const float*, void*, void*, int64_t, int, float,
                            hipStream_t);
@@ -74,20 +70,6 @@ void launch_gather_multi(int, const void**, void**, const int*,
 void launch_gather_multi_dyn(int, const void**, void**, const int*,
                              const int32_t*, const int32_t*, int64_t,
                              hipStream_t);
-void launch_gemm_bf16_skinny(const void*, const void*, const float*, void*,
-                             int, int, int, int, hipStream_t);
-int launch_gemm_bf16_k64(const void*, const void*, const float*, void*, int,
-                         int, int, int, hipStream_t);
-int launch_gemm_bf16_k64s(const void*, const void*, const float*, void*,
-                          int, int, int, int, hipStream_t);
-int launch_gemm_bf16_k64p(const void*, const void*, const float*, void*,
-                          int, int, int, int, hipStream_t);
-int launch_gemm_bf16_k64w(const void*, const void*, const float*, void*,
-                          int, int, int, int, hipStream_t);
-int launch_gemm_bf16_k64s3(const void*, const void*, const float*, void*,
-                          int, int, int, int, hipStream_t);
-int launch_gemm_bf16_k64d(const void*, const void*, const float*, void*,
-                          int, int, int, int, hipStream_t);
 void launch_gen_fields(float*, int64_t*, int64_t, const float*, const float*,
                        int, int64_t, int64_t, unsigned long long*,
                        hipStream_t);
@@ -394,57 +376,48 @@ torch::Tensor check_gemm_args(const torch::Tensor& A, const torch::Tensor& Bt,
   return device_vec_f32(bias, Bt.size(0), "bias");
 }
 
+GemmArgs gemm_args(const torch::Tensor& A, const torch::Tensor& Bt,
+                   const torch::Tensor& bias_f, torch::Tensor& C,
+                   int64_t act) {
+  return GemmArgs{A.data_ptr(), Bt.data_ptr(),
+                  bias_f.defined() ? bias_f.data_ptr<float>() : nullptr,
+                  C.data_ptr(), (int)A.size(0), (int)Bt.size(0),
+                  (int)A.size(1), (int)act, cur_stream()};
+}
+
 torch::Tensor gemm_bf16(torch::Tensor A, torch::Tensor Bt,
                         c10::optional<torch::Tensor> bias, int64_t act) {
   auto bias_f = check_gemm_args(A, Bt, bias);
   int64_t M = A.size(0), K = A.size(1), N = Bt.size(0);
   auto C = torch::empty({M, N}, A.options());
   if (M == 0 || N == 0) return C;  // a zero-size grid is a launch error
-  const float* bias_ptr =
-      bias_f.defined() ? bias_f.data_ptr<float>() : nullptr;
+  GemmArgs g = gemm_args(A, Bt, bias_f, C, act);
   // measured dispatch (profiles/ r02/r06 GEMM tables): big square shapes →
-  // 8-phase BM=256+swizzle; chip-filling mid shapes → 8-phase BM=128+swizzle;
-  // everything else → the 128² single-buffer tile.
+  // 8-phase BM=256+swizzle; everything else → the 128² / 64² tile family.
+  // NOTE: 8-phase BM128+swz wins STANDALONE at BERT shapes (+8-16%) but
+  // measured ~2% slower in-context (L2-warm inputs; see profiles/ r06) — so
+  // only the big-shape case dispatches to the pipelined kernel.
   int64_t t256 = ((M + 255) / 256) * ((N + 255) / 256);
-  int64_t t128 = ((M + 127) / 128) * ((N + 255) / 256);
-  // NOTE: BM128+swz wins STANDALONE at BERT shapes (+8-16%) but measured
-  // ~2% slower in-context (L2-warm inputs; see profiles/ r06) — so only the
-  // big-shape case dispatches to the pipelined kernel.
-  (void)t128;
-  int swz_code = -1;
-  if (t256 >= 128 && K >= 1536 && N >= 2048)
-    swz_code = 1;  // BM256 + swizzle
-  int rc = swz_code >= 0
-               ? launch_gemm_bf16_8p(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                     C.data_ptr(), (int)M, (int)N, (int)K,
-                                     (int)act, swz_code, cur_stream())
-               : -1;
-  if (rc != 0) {
+  int rc = (t256 >= 128 && K >= 1536 && N >= 2048)
+               ? launch_gemm_bf16(GEMM_8P256S, &g)
+               : GEMM_BAD_SHAPE;
+  if (rc != GEMM_OK) {
     // narrow outputs: the 128² grid can't fill 256 CUs (e.g. [8192,256] →
     // 128 blocks); the 64² tile quadruples the grid (profiles r2)
     int64_t t128grid = ((M + 127) / 128) * ((N + 127) / 128);
     if (t128grid < 208) {
-      launch_gemm_bf16_skinny(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                              C.data_ptr(), (int)M, (int)N, (int)K,
-                              (int)act, cur_stream());
+      rc = launch_gemm_bf16(GEMM_SKINNY, &g);
     } else {
       // K%64==0 (BERT fc1/QKV/fc2 class): the swizzled BK=64 tile wins
       // 6-21% over BK=32 at every such shape measured (profiles r2
       // bench_gemm_k64; register staging + XOR chunk swizzle — the linear
       // layout's 128B-period LDS alias cost ~4e5 bank conflicts/dispatch).
       // Big squares already went to the 8-phase kernel above.
-      int rc2 = (K % 64 == 0)
-                    ? launch_gemm_bf16_k64s(A.data_ptr(), Bt.data_ptr(),
-                                            bias_ptr, C.data_ptr(), (int)M,
-                                            (int)N, (int)K, (int)act,
-                                            cur_stream())
-                    : -1;
-      if (rc2 != 0)
-        launch_gemm_bf16(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                         C.data_ptr(), (int)M, (int)N, (int)K, (int)act,
-                         cur_stream());
+      rc = (K % 64 == 0) ? launch_gemm_bf16(GEMM_K64S, &g) : GEMM_BAD_SHAPE;
+      if (rc != GEMM_OK) rc = launch_gemm_bf16(GEMM_BK32, &g);
     }
   }
+  TORCH_CHECK(rc == GEMM_OK, "gemm_bf16: no kernel for this shape");
   return C;
 }
 
@@ -586,66 +559,20 @@ void featpack(std::vector<torch::Tensor> srcs, torch::Tensor out) {
                   cur_stream());
 }
 
+// one named kernel of the family (GemmVariant, gemm_api.h) — the A/B hook
+// for tests, tools/ and the ARKFLOW_GEMM_VARIANT override
 torch::Tensor gemm_bf16_variant(torch::Tensor A, torch::Tensor Bt,
                                 c10::optional<torch::Tensor> bias,
                                 int64_t act, int64_t variant) {
-  // variant: 0 = 128² tile, 1 = 8-phase linear LDS, 2 = 8-phase + swizzle
   auto bias_f = check_gemm_args(A, Bt, bias);
-  int64_t M = A.size(0), K = A.size(1), N = Bt.size(0);
-  auto C = torch::empty({M, N}, A.options());
-  if (M == 0 || N == 0) return C;
-  const float* bias_ptr =
-      bias_f.defined() ? bias_f.data_ptr<float>() : nullptr;
-  if (variant == 0) {
-    launch_gemm_bf16(A.data_ptr(), Bt.data_ptr(), bias_ptr, C.data_ptr(),
-                     (int)M, (int)N, (int)K, (int)act, cur_stream());
-  } else if (variant == 3) {
-    int rc = launch_gemm_bf16_2p(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                 C.data_ptr(), (int)M, (int)N, (int)K,
-                                 (int)act, cur_stream());
-    TORCH_CHECK(rc == 0, "shape not supported by 2-phase kernel");
-  } else if (variant == 6) {
-    launch_gemm_bf16_skinny(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                            C.data_ptr(), (int)M, (int)N, (int)K, (int)act,
-                            cur_stream());
-  } else if (variant == 7) {
-    int rc = launch_gemm_bf16_k64(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                  C.data_ptr(), (int)M, (int)N, (int)K,
-                                  (int)act, cur_stream());
-    TORCH_CHECK(rc == 0, "K must be a multiple of 64 for the BK=64 kernel");
-  } else if (variant == 8) {
-    int rc = launch_gemm_bf16_k64s(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                   C.data_ptr(), (int)M, (int)N, (int)K,
-                                   (int)act, cur_stream());
-    TORCH_CHECK(rc == 0, "K must be a multiple of 64 for the BK=64 kernel");
-  } else if (variant == 10) {
-    TORCH_CHECK(launch_gemm_bf16_k64p(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                      C.data_ptr(), (int)M, (int)N, (int)K,
-                                      (int)act, cur_stream()) == 0,
-                "k64p requires K % 64 == 0");
-  } else if (variant == 11) {
-    TORCH_CHECK(launch_gemm_bf16_k64w(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                      C.data_ptr(), (int)M, (int)N, (int)K,
-                                      (int)act, cur_stream()) == 0,
-                "k64w requires K % 64 == 0");
-  } else if (variant == 12) {
-    TORCH_CHECK(launch_gemm_bf16_k64s3(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                       C.data_ptr(), (int)M, (int)N, (int)K,
-                                       (int)act, cur_stream()) == 0,
-                "k64s3 requires K % 64 == 0");
-  } else if (variant == 9) {
-    int rc = launch_gemm_bf16_k64d(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                   C.data_ptr(), (int)M, (int)N, (int)K,
-                                   (int)act, cur_stream());
-    TORCH_CHECK(rc == 0, "K must be a multiple of 64 for the BK=64 kernel");
-  } else {
-    // 8-phase variants: 1=BM256, 2=BM256+swz, 4=BM128, 5=BM128+swz
-    int swz_code = variant == 2 ? 1 : variant == 4 ? 2 : variant == 5 ? 3 : 0;
-    int rc = launch_gemm_bf16_8p(A.data_ptr(), Bt.data_ptr(), bias_ptr,
-                                 C.data_ptr(), (int)M, (int)N, (int)K,
-                                 (int)act, swz_code, cur_stream());
-    TORCH_CHECK(rc == 0, "shape not supported by 8-phase kernel");
-  }
+  auto C = torch::empty({A.size(0), Bt.size(0)}, A.options());
+  if (C.numel() == 0) return C;
+  GemmArgs g = gemm_args(A, Bt, bias_f, C, act);
+  int rc = variant == (int)variant ? launch_gemm_bf16((int)variant, &g)
+                                   : (int)GEMM_BAD_VARIANT;
+  TORCH_CHECK(rc != GEMM_BAD_VARIANT, "unknown gemm variant ", variant);
+  TORCH_CHECK(rc == GEMM_OK, "K = ", g.K,
+              " not supported by gemm variant ", variant);
   return C;
 }
 

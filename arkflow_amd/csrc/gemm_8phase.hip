@@ -18,10 +18,7 @@
 //
 // Dispatched for N-tile counts that fill the chip; the 128² kernel
 // (gemm_bf16.hip) remains for small shapes and edges.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "gemm_common.h"
 
 #define P8_THREADS 512
 #define P8_BN 256
@@ -29,22 +26,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // B half-tile = 128 rows × 64 cols bf16 = 16 KiB = 2 global_load_lds/thread;
 // A half-tile = (BM/2) rows — 16 KiB at BM=256, 8 KiB at BM=128 (1 load).
 #define B_HALF_BYTES (128 * 64 * 2)
-
-enum Act8 { A8_NONE = 0, A8_RELU = 1, A8_GELU = 2, A8_SILU = 3 };
-
-DEV_INLINE float apply_act8(float x, int act) {
-  switch (act) {
-    case A8_RELU: return fmaxf(x, 0.f);
-    case A8_GELU: {
-      float c = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-      c = fminf(fmaxf(c, -10.f), 10.f);  // saturate: no overflow in expf
-      float e = __expf(2.f * c);
-      return 0.5f * x * (1.f + (e - 1.f) / (e + 1.f));
-    }
-    case A8_SILU: return x / (1.f + __expf(-x));
-    default: return x;
-  }
-}
 
 // XOR swizzle (involution, 16B-block preserving): fold the row's low 3 bits
 // (byte bits 7-9 at the 128-byte row stride) into bank bits 4-6 — spreads a
@@ -74,13 +55,7 @@ void gemm_bf16_8p_kernel(const __bf16* __restrict__ A,   // [M,K]
                  : (size_t)half * A_HALF);
   };
 
-  int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  if (nwg >= 16) {  // bijective XCD swizzle (guide m204)
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = bid % 8, off = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + off;
-  }
+  const int bid = xcd_block_id();
   const int bm = bid / tiles_n, bn = bid % tiles_n;
   const int row0 = bm * BMT, col0 = bn * P8_BN;
 
@@ -181,7 +156,25 @@ void gemm_bf16_8p_kernel(const __bf16* __restrict__ A,   // [M,K]
     }
   };
 
-#define P8_MFMA(ASEL2, BSEL2, BF)                                              do {                                                                            __builtin_amdgcn_s_barrier();                                                 asm volatile("s_waitcnt lgkmcnt(0)");                                         __builtin_amdgcn_sched_barrier(0);                                            __builtin_amdgcn_s_setprio(1);                                                _Pragma("unroll") for (int q = 0; q < 4; ++q)                                     _Pragma("unroll") for (int r = 0; r < 2; ++r)                                     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                  acc[(ASEL2)*4 + q][(BSEL2)*2 + r] =                                               __builtin_amdgcn_mfma_f32_16x16x32_bf16(                                          a_frag[q][ks], (BF)[r][ks],                                                   acc[(ASEL2)*4 + q][(BSEL2)*2 + r], 0, 0, 0);              __builtin_amdgcn_s_setprio(0);                                                __builtin_amdgcn_sched_barrier(0);                                            __builtin_amdgcn_s_barrier();                                               } while (0)
+// one quadrant phase's compute: barrier → fragments landed → prioritised
+// MFMA×16 (×8 at BM=128) → barrier
+#define P8_MFMA(ASEL2, BSEL2, BF)                                  \
+  do {                                                             \
+    __builtin_amdgcn_s_barrier();                                  \
+    asm volatile("s_waitcnt lgkmcnt(0)");                          \
+    __builtin_amdgcn_sched_barrier(0);                             \
+    __builtin_amdgcn_s_setprio(1);                                 \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q)                  \
+      _Pragma("unroll") for (int r = 0; r < 2; ++r)                \
+        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)           \
+          acc[(ASEL2)*4 + q][(BSEL2)*2 + r] =                      \
+              __builtin_amdgcn_mfma_f32_16x16x32_bf16(             \
+                  a_frag[q][ks], (BF)[r][ks],                      \
+                  acc[(ASEL2)*4 + q][(BSEL2)*2 + r], 0, 0, 0);     \
+    __builtin_amdgcn_s_setprio(0);                                 \
+    __builtin_amdgcn_sched_barrier(0);                             \
+    __builtin_amdgcn_s_barrier();                                  \
+  } while (0)
 
   for (int t = 0; t < NT; ++t) {
     const int buf = t & 1;
@@ -226,110 +219,35 @@ void gemm_bf16_8p_kernel(const __bf16* __restrict__ A,   // [M,K]
   }
 #undef P8_MFMA
 
-  // ---- epilogue: bias + activation, bf16 stores (bounds-checked) -----------
-  const int c_row_in_frag = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 2 * QF; ++i) {
-    int asel = i / QF, q = i % QF;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int bsel = j >> 1, r2 = j & 1;
-      int col = col0 + bsel * 128 + r2 * 64 + wn * 16 + fr;
-      if (col >= N) continue;
-      float b = HAS_BIAS ? bias[col] : 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        int row = row0 + asel * RH + q * 32 + wm * 16 + c_row_in_frag + rr;
-        if (row >= M) continue;
-        float v = acc[i][j][rr] + b;
-        C[(int64_t)row * N + col] = (__bf16)apply_act8(v, ACT);
-      }
+  // ---- epilogue: the interleaved fragment layout of the header comment ----
+  store_frags<ACT, HAS_BIAS>(
+      acc, bias, C, M, N,
+      [&](int i) { return row0 + (i / QF) * RH + (i % QF) * 32 + wm * 16; },
+      [&](int j) { return col0 + (j >> 1) * 128 + (j & 1) * 64 + wn * 16; });
+}
+
+template <int BMT, bool SWZ>
+static void launch_8p(const GemmArgs& g) {
+  constexpr size_t lds = 2 * (2 * (size_t)(BMT / 2) * 64 * 2 + 2 * B_HALF_BYTES);
+  dispatch_epilogue(g.act, g.bias != nullptr, [&](auto act, auto has_bias) {
+    auto kernel = gemm_bf16_8p_kernel<BMT, decltype(act)::value,
+                                      decltype(has_bias)::value, SWZ>;
+    // > 64 KiB of dynamic LDS needs the opt-in once per instantiation
+    static bool attr_done = false;
+    if (!attr_done) {
+      (void)hipFuncSetAttribute(
+          (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+          (int)lds);
+      attr_done = true;
     }
-  }
+    launch_tiles<BMT, P8_BN>(kernel, P8_THREADS, lds, g);
+  });
 }
 
-template <int BMT, int ACT, bool HAS_BIAS, bool SWZ>
-static void launch_one_8p(const void* A, const void* Bt, const float* bias,
-                          void* C, int M, int N, int K, int tiles_n,
-                          dim3 grid, dim3 block, size_t lds_bytes,
-                          hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute(
-        (const void*)gemm_bf16_8p_kernel<BMT, ACT, HAS_BIAS, SWZ>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    attr_done = true;
-  }
-  gemm_bf16_8p_kernel<BMT, ACT, HAS_BIAS, SWZ><<<grid, block, lds_bytes,
-                                                 st>>>(
-      (const __bf16*)A, (const __bf16*)Bt, bias, (__bf16*)C, M, N, K,
-      tiles_n);
+int launch_gemm_bf16_8p(const GemmArgs& g, int bm, bool swz) {
+  if (g.K % P8_BK != 0 || g.K / P8_BK < 3) return GEMM_BAD_SHAPE;
+  // BM=128 is the chip-filling tile at narrow N
+  if (bm == 128) swz ? launch_8p<128, true>(g) : launch_8p<128, false>(g);
+  else           swz ? launch_8p<256, true>(g) : launch_8p<256, false>(g);
+  return GEMM_OK;
 }
-
-template <int BMT, int ACT>
-static void dispatch_bias_swz(const void* A, const void* Bt,
-                              const float* bias, void* C, int M, int N,
-                              int K, int tiles_n, dim3 grid, dim3 block,
-                              size_t lds, int swz, hipStream_t st) {
-  if (bias) {
-    if (swz)
-      launch_one_8p<BMT, ACT, true, true>(A, Bt, bias, C, M, N, K, tiles_n,
-                                          grid, block, lds, st);
-    else
-      launch_one_8p<BMT, ACT, true, false>(A, Bt, bias, C, M, N, K, tiles_n,
-                                           grid, block, lds, st);
-  } else {
-    if (swz)
-      launch_one_8p<BMT, ACT, false, true>(A, Bt, bias, C, M, N, K, tiles_n,
-                                           grid, block, lds, st);
-    else
-      launch_one_8p<BMT, ACT, false, false>(A, Bt, bias, C, M, N, K,
-                                            tiles_n, grid, block, lds, st);
-  }
-}
-
-template <int BMT>
-static void dispatch_act(const void* A, const void* Bt, const float* bias,
-                         void* C, int M, int N, int K, int act, int swz,
-                         hipStream_t st) {
-  int tiles_m = (M + BMT - 1) / BMT;
-  int tiles_n = (N + P8_BN - 1) / P8_BN;
-  size_t lds = 2 * (2 * (size_t)(BMT / 2) * 64 * 2 + 2 * B_HALF_BYTES);
-  dim3 grid(tiles_m * tiles_n), block(P8_THREADS);
-  switch (act) {
-    case A8_RELU:
-      dispatch_bias_swz<BMT, A8_RELU>(A, Bt, bias, C, M, N, K, tiles_n, grid,
-                                      block, lds, swz, st);
-      break;
-    case A8_GELU:
-      dispatch_bias_swz<BMT, A8_GELU>(A, Bt, bias, C, M, N, K, tiles_n, grid,
-                                      block, lds, swz, st);
-      break;
-    case A8_SILU:
-      dispatch_bias_swz<BMT, A8_SILU>(A, Bt, bias, C, M, N, K, tiles_n, grid,
-                                      block, lds, swz, st);
-      break;
-    default:
-      dispatch_bias_swz<BMT, A8_NONE>(A, Bt, bias, C, M, N, K, tiles_n, grid,
-                                      block, lds, swz, st);
-      break;
-  }
-}
-
-extern "C" {
-
-// returns 0 if dispatched, -1 if the shape doesn't fit this kernel
-int launch_gemm_bf16_8p(const void* A, const void* Bt, const float* bias,
-                        void* C, int M, int N, int K, int act, int swz,
-                        hipStream_t st) {
-  if (K % P8_BK != 0 || K / P8_BK < 3) return -1;
-  // swz>=2 forces the BM=128 tile (chip-filling at narrow N)
-  if (swz >= 2) {
-    dispatch_act<128>(A, Bt, bias, C, M, N, K, act, swz == 3 ? 1 : 0, st);
-  } else {
-    dispatch_act<256>(A, Bt, bias, C, M, N, K, act, swz, st);
-  }
-  return 0;
-}
-
-}  // extern "C"

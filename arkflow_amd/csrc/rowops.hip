@@ -1,7 +1,7 @@
 // Row-wise bf16 ops for the inference processor: LayerNorm (with optional
 // fused residual add) and row softmax. Memory-bound → vectorized short4/short8
 // loads per guide Guideline 13; one block per row, wave+LDS reductions.
-#include "common.h"
+#include "gemm_common.h"  // Act / apply_act: the GEMM epilogues' formula
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(8))) __bf16 vbf16x8;
@@ -287,18 +287,7 @@ __global__ void bias_act_bf16_kernel(const __bf16* __restrict__ x,
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     float v = (float)x[i] + (bias ? bias[i % n] : 0.f);
-    switch (act) {
-      case 1: v = fmaxf(v, 0.f); break;
-      case 2: {
-        float c = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-        c = fminf(fmaxf(c, -10.f), 10.f);
-        float e = __expf(2.f * c);
-        v = 0.5f * v * (1.f + (e - 1.f) / (e + 1.f));
-        break;
-      }
-      case 3: v = v / (1.f + __expf(-v)); break;
-    }
-    out[i] = (__bf16)v;
+    out[i] = (__bf16)apply_act(v, act);
   }
 }
 

@@ -27,8 +27,9 @@ ACT_NAMES = {0: "none", 1: "relu", 2: "gelu", 3: "silu"}
 # bound on the activation's slope (how much it can amplify an error in z)
 ACT_SLOPE = {ACT_NONE: 1.0, ACT_RELU: 1.0, ACT_GELU: 1.13, ACT_SILU: 1.1}
 
-# Absolute error of the kernels' own activation formulas (apply_act in
-# csrc/gemm_bf16.hip: tanh-GELU through exp(2c) with c clamped to +-10, SiLU
+# Absolute error of the kernels' own activation formula (apply_act in
+# csrc/gemm_common.h, the one copy every GEMM epilogue and bias_act_bf16 call:
+# tanh-GELU through exp(2c) with c clamped to +-10, SiLU
 # as x / (1 + exp(-x))) evaluated in fp32 torch against exact fp64 tanh-GELU
 # and SiLU on a 2,400,001-point grid over [-12, 12]: the maximum absolute
 # difference is 1.157e-6 (SiLU, the fp32 rounding of outputs near 12; GELU
@@ -148,8 +149,9 @@ def gemm_emulate(A, Bt, bias, act):
     return kernel_act_f32(z, act).to(BF16)
 
 
-# variant id -> (BM, BN, K values): tile sizes read from csrc/gemm_bf16.hip
-# and csrc/gemm_8phase.hip; K values are multiples of the variant's BK from
+# variant id (GemmVariant in csrc/gemm_api.h) -> (BM, BN, K values): tile
+# sizes read from the launch_tiles<BM, BN> calls in csrc/gemm_bf16.hip and
+# csrc/gemm_8phase.hip; K values are multiples of the variant's BK from
 # the launcher's minimum K-tile count upwards.
 GEMM_VARIANTS = {
     0: (128, 128, (32, 64, 160)),        # 128^2 BK=32 (dispatcher fall-through)
@@ -221,6 +223,9 @@ GEMM_DISPATCH_CASES = [
     GemmCase("skinny-300x257x96", None, "d", 300, 257, 96, ACT_GELU, True,
              504),
 ]
+# the variant id each of those branches is documented to take (bindings.cpp
+# gemm_bf16: GEMM_8P256S, GEMM_BK32, GEMM_K64S, GEMM_SKINNY)
+GEMM_DISPATCH_VARIANTS = [2, 0, 8, 6]
 
 
 def gemm_inputs(case):

@@ -71,6 +71,19 @@ def test_gemm_dispatch_branch(nat, dev, case):
     R.assert_within(C, ref, tol, case.id, tile=(128, 128))
 
 
+@pytest.mark.parametrize("case,variant",
+                         zip(R.GEMM_DISPATCH_CASES, R.GEMM_DISPATCH_VARIANTS),
+                         ids=lambda p: getattr(p, "id", str(p)))
+def test_gemm_dispatch_takes_documented_variant(nat, dev, case, variant):
+    """gemm_bf16 runs the kernel its branch names: bitwise equal to
+    gemm_bf16_variant with that id (pins the dispatcher-to-enum wiring)."""
+    A, Bt, bias = _to(dev, *R.gemm_inputs(case))
+    C = nat.gemm_bf16(A, Bt, bias, case.act)
+    Cv = nat.gemm_bf16_variant(A, Bt, bias, case.act, variant)
+    assert torch.equal(C, Cv), \
+        f"{case.id}: gemm_bf16 differs bitwise from variant {variant}"
+
+
 # ------------------------------------------------------------------- LayerNorm
 def _check_ln(nat, dev, x, res, gamma, beta, what):
     x, res, gamma, beta = _to(dev, x, res, gamma, beta)
@@ -268,6 +281,9 @@ def test_bad_arguments_raise_before_launch(nat, dev):
             call(A.reshape(2, 2, 64), Bt, None)
         with pytest.raises(RuntimeError):  # host bias
             call(A, Bt, bias.cpu())
+    for variant in (99, -1):
+        with pytest.raises(RuntimeError):  # not a variant id
+            nat.gemm_bf16_variant(A, Bt, bias, 0, variant)
     x = torch.randn(3, 64, device=dev).to(bf)
     g = torch.randn(64, device=dev)
     b = torch.randn(64, device=dev)
