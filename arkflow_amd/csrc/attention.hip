@@ -7,6 +7,7 @@
 // LDS: K [S][D+4] + V^T [D][S+4] staged once (padded rows: +4 bf16 = 2-bank
 // row stride → conflict-free ds_read_b128), P bf16 [32][S+4] per wave.
 #include "common.h"
+#include "kernels_api.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -154,10 +155,6 @@ void attention_kernel(const __bf16* __restrict__ Q,
         Ob[(int64_t)row * ldo + col] = (__bf16)acc2[am][nd][r];
       }
 }
-
-extern "C" int launch_attention_flash(const void*, const void*,
-                                      const void*, void*, int, int, int,
-                                      float, int, int, int, hipStream_t);
 
 extern "C" {
 

@@ -9,129 +9,10 @@
 #include <tuple>
 #include <vector>
 
-#include "gemm_api.h"  // GemmVariant, GemmArgs, launch_gemm_bf16
-
-// ---- extern kernel launchers (defined in the .hip TUs) ----------------------
-extern "C" {
-int filter_grid(int64_t n);
-void launch_filter_count_f32(const float*, int64_t, int, float, int32_t*,
-                             hipStream_t);
-void launch_filter_scatter_f32(const float*, int64_t, int, float,
-                               const int32_t*, int32_t*, hipStream_t);
-void launch_filter_count_i64(const int64_t*, int64_t, int, int64_t, int32_t*,
-                             hipStream_t);
-void launch_filter_scatter_i64(const int64_t*, int64_t, int, int64_t,
-                               const int32_t*, int32_t*, hipStream_t);
-void launch_mask_count(const bool*, int64_t, int32_t*, hipStream_t);
-void launch_mask_scatter(const bool*, int64_t, const int32_t*, int32_t*,
-                         hipStream_t);
-void launch_gather(const void*, const int32_t*, int64_t, void*, int,
-                   hipStream_t);
-void launch_hash_build(const int64_t*, int64_t, int64_t*, int32_t*, uint32_t,
-                       int32_t*, int32_t*, hipStream_t);
-void launch_hash_export(const int64_t*, const int32_t*, uint32_t, int64_t*,
-                        hipStream_t);
-void launch_segment_reduce_f32(const float*, const int32_t*, int64_t, int, int,
-                               float*, int32_t*, hipStream_t);
-void launch_hash_agg_capture(const int64_t*, const int32_t*, int64_t,
-                             int64_t*, int32_t*, uint32_t, int32_t*, int32_t*,
-                             float*, int, const float* const*, const int*,
-                             float* const*, int32_t* const*, int, int64_t*,
-                             int64_t*, int32_t*, hipStream_t);
-void launch_join_build(const int64_t*, int64_t, int64_t*, int32_t*, int32_t*,
-                       uint32_t, hipStream_t);
-void launch_join_probe_count(const int64_t*, int64_t, const int64_t*,
-                             const int32_t*, const int32_t*, const int64_t*,
-                             uint32_t, int32_t*, hipStream_t);
-void launch_join_probe_emit(const int64_t*, int64_t, const int64_t*,
-                            const int32_t*, const int32_t*, const int64_t*,
-                            uint32_t, const int32_t*, int64_t*, int64_t*,
-                            hipStream_t);
-void launch_layernorm_bf16(const void*, const void*, const float*,
-                           const float*, void*, void*, int64_t, int, float,
-                           hipStream_t);
-void launch_softmax_bf16(const void*, void*, int64_t, int, float, hipStream_t);
-void launch_bias_act_bf16(const void*, const float*, void*, int64_t, int, int,
-                          hipStream_t);
-int launch_attention_bf16(const void*, const void*, const void*, void*, int,
-                          int, int, float, hipStream_t);
-int launch_attention_qkv_bf16(const void*, void*, int, int, int, int, float,
-                              hipStream_t);
-int launch_attention_qkv_bf16_pad(const void*, void*, int, int, int, int,
-                                  float, int, hipStream_t);
-void launch_proto_copy_bytes(const uint8_t*, const int64_t*, const int64_t*,
-                             int64_t, uint8_t*, hipStream_t);
-void launch_proto_decode(const uint8_t*, const int64_t*, int64_t, int,
-                         const int*, const int*, const int*, const int*,
-                         int64_t*, double*, int64_t*, int32_t*, int32_t*,
-                         hipStream_t);
-void launch_gather_multi(int, const void**, void**, const int*,
-                         const int32_t*, int64_t, hipStream_t);
-void launch_gather_multi_dyn(int, const void**, void**, const int*,
-                             const int32_t*, const int32_t*, int64_t,
-                             hipStream_t);
-void launch_gen_fields(float*, int64_t*, int64_t, const float*, const float*,
-                       int, int64_t, int64_t, unsigned long long*,
-                       hipStream_t);
-int launch_genfiltpack(const float*, const float*, int, int64_t, int64_t,
-                       int64_t, int, int, float, float* const*, int64_t*,
-                       void*, int, int32_t*, int32_t*, unsigned long long*,
-                       unsigned long long*, hipStream_t);
-void launch_scan_counts(const int32_t*, int, int32_t*, int32_t*,
-                        hipStream_t);
-void launch_featpack(const float**, int, int, int64_t, void*, hipStream_t);
-void launch_featpack64(const double**, int, int, int64_t, void*,
-                       hipStream_t);
-void launch_gemv_bf16_f32(const void*, const void*, float, int64_t, int,
-                          float*, hipStream_t);
-void launch_bytes_hash(const uint8_t*, const int64_t*, int64_t, int64_t*,
-                       hipStream_t);
-void launch_bytes_match(const uint8_t*, const int64_t*, int64_t,
-                        const uint8_t*, int, int, bool*, hipStream_t);
-int scan_grid(int64_t n);
-void launch_scan_partials(const int32_t*, int64_t, int64_t*, hipStream_t);
-void launch_scan_boffs64(const int64_t*, int, int64_t*, int64_t*,
-                         hipStream_t);
-void launch_scan_write(const int32_t*, int64_t, const int64_t*, int64_t*,
-                       hipStream_t);
-int radix_sort_nblocks(int64_t);
-int onesweep_nblocks(int64_t);
-void launch_os_hist256_u32(const uint32_t*, int64_t, int, int32_t*, int,
-                           hipStream_t);
-void launch_os_hist256_u64(const uint64_t*, int64_t, int, int32_t*, int,
-                           hipStream_t);
-void launch_onesweep_pass_u32(const uint32_t*, const int32_t*, uint32_t*,
-                              int32_t*, int64_t, int, const int32_t*, int,
-                              hipStream_t);
-void launch_onesweep_pass_u64(const uint64_t*, const int32_t*, uint64_t*,
-                              int32_t*, int64_t, int, const int32_t*, int,
-                              hipStream_t);
-void launch_i32_to_ordered(const int32_t*, uint32_t*, int64_t, int,
-                           hipStream_t);
-void launch_radix_hist_u32(const uint32_t*, const int32_t*, int64_t, int,
-                           int32_t*, int, hipStream_t);
-void launch_radix_scatter_u32(const uint32_t*, const int32_t*, int64_t, int,
-                              const int32_t*, int, int32_t*, hipStream_t);
-void launch_radix_hist_u64(const uint64_t*, const int32_t*, int64_t, int,
-                           int32_t*, int, hipStream_t);
-void launch_radix_scatter_u64(const uint64_t*, const int32_t*, int64_t, int,
-                              const int32_t*, int, int32_t*, hipStream_t);
-void launch_f32_to_ordered(const float*, uint32_t*, int64_t, int,
-                           hipStream_t);
-void launch_i64_to_ordered(const int64_t*, uint64_t*, int64_t, int,
-                           hipStream_t);
-void launch_json_decode(const uint8_t*, const int64_t*, int64_t, int,
-                        const char*, const int*, const int*, const int*,
-                        const int*, int, const char*, const int*,
-                        double*, int64_t*, int64_t*, int32_t*, uint8_t*,
-                        int32_t*, int32_t*, int, hipStream_t);
-void launch_json_copy_strings(const uint8_t*, const int64_t*, const int64_t*,
-                              const uint8_t*, int64_t, int64_t, uint8_t*,
-                              hipStream_t);
-void launch_json_copy_strings_wave(const uint8_t*, const int64_t*,
-                                   const int64_t*, const uint8_t*, int64_t,
-                                   int64_t, uint8_t*, hipStream_t);
-}
+// kernel launchers, each declared in the header its defining .hip includes
+#include "gemm_api.h"        // GemmVariant, GemmArgs, launch_gemm_bf16
+#include "kernels_api.h"     // inference, decode, fused step
+#include "relational_api.h"  // filter, gather, group-by, join, sort, scans
 
 namespace {
 
@@ -190,56 +71,100 @@ std::tuple<torch::Tensor, torch::Tensor> exscan(const torch::Tensor& counts) {
 }
 
 // ---------------------------------------------------------------------- filter
+// `col OP scalar` over an f32 or i64 column (callers widen or reject the rest)
+Predicate cmp_predicate(const torch::Tensor& col, int64_t op, double scalar) {
+  bool is_f32 = col.scalar_type() == torch::kFloat32;
+  return {is_f32 ? PRED_F32 : PRED_I64, col.data_ptr(), (int)op, scalar};
+}
+
+// Order-preserving compaction of the n > 0 rows that satisfy pred: block
+// counts → scan → scatter of row indices (int32).
+// count_out null — sync form: the total is read back (the one host sync) and
+// the index tensor has exactly `total` entries.
+// count_out set — capture form: the total goes to *count_out on the device,
+// the index tensor has n entries of which the first *count_out are valid, and
+// the returned total is -1.
+std::tuple<torch::Tensor, int64_t> compact(const Predicate& pred, int64_t n,
+                                           const torch::TensorOptions& opts32,
+                                           torch::Tensor* count_out) {
+  auto st = cur_stream();
+  int nblocks = filter_grid(n);
+  auto counts = torch::empty({nblocks}, opts32);
+  launch_compact_count(&pred, n, counts.data_ptr<int32_t>(), st);
+  torch::Tensor offs;
+  int64_t total = -1;
+  if (count_out && nblocks <= 1024) {
+    // single-block scan writes offsets AND the device total in one launch
+    // (replaces torch cumsum + sub + copy_ — 3 kernels → 1 in the graph)
+    offs = torch::empty({nblocks}, opts32);
+    launch_scan_counts(counts.data_ptr<int32_t>(), nblocks,
+                       offs.data_ptr<int32_t>(),
+                       count_out->data_ptr<int32_t>(), st);
+  } else {
+    auto [offs2, total_t] = exscan(counts);
+    offs = offs2;
+    if (count_out)
+      count_out->copy_(total_t, /*non_blocking=*/true);
+    else
+      total = total_t.item<int32_t>();
+  }
+  auto idx = torch::empty({count_out ? n : total}, opts32);
+  if (count_out || total > 0)
+    launch_compact_scatter(&pred, n, offs.data_ptr<int32_t>(),
+                           idx.data_ptr<int32_t>(), st);
+  return {idx, total};
+}
+
+// Rows idx[0..m) of every column, 32 columns per launch, into `outs` — or,
+// where `outs` is empty, into fresh m-row tensors. With count_dev the row
+// count is read on the device (capture form) and m is its upper bound.
+std::vector<torch::Tensor> gather_multi(const std::vector<torch::Tensor>& cols,
+                                        const torch::Tensor& idx, int64_t m,
+                                        const int32_t* count_dev,
+                                        std::vector<torch::Tensor> outs) {
+  bool fresh = outs.empty();
+  if (fresh) outs.reserve(cols.size());
+  std::vector<const void*> src;
+  std::vector<void*> dst;
+  std::vector<int> esz;
+  auto flush = [&]() {
+    if (!src.empty() && m > 0)
+      launch_gather_multi((int)src.size(), src.data(), dst.data(), esz.data(),
+                          idx.data_ptr<int32_t>(), m, count_dev, cur_stream());
+    src.clear(); dst.clear(); esz.clear();
+  };
+  for (size_t c = 0; c < cols.size(); ++c) {
+    if (fresh) outs.push_back(torch::empty({m}, cols[c].options()));
+    src.push_back(cols[c].data_ptr());
+    dst.push_back(outs[c].data_ptr());
+    esz.push_back((int)cols[c].element_size());
+    if ((int)src.size() == 32) flush();
+  }
+  flush();
+  return outs;
+}
+
 torch::Tensor mask_to_indices(torch::Tensor mask) {
   check_cuda(mask, "mask");
   TORCH_CHECK(mask.scalar_type() == torch::kBool, "mask must be bool");
   int64_t n = mask.numel();
-  auto st = cur_stream();
-  int nblocks = filter_grid(n);
-  auto counts = torch::empty({std::max(nblocks, 1)},
-                             mask.options().dtype(torch::kInt32));
-  if (n == 0) return torch::empty({0}, mask.options().dtype(torch::kInt32));
-  launch_mask_count(mask.data_ptr<bool>(), n, counts.data_ptr<int32_t>(), st);
-  auto [offs, total_t] = exscan(counts);
-  int64_t total = total_t.item<int32_t>();  // one device sync per filter op
-  auto out = torch::empty({total}, mask.options().dtype(torch::kInt32));
-  if (total)
-    launch_mask_scatter(mask.data_ptr<bool>(), n, offs.data_ptr<int32_t>(),
-                        out.data_ptr<int32_t>(), st);
-  return out;
+  auto opts32 = mask.options().dtype(torch::kInt32);
+  if (n == 0) return torch::empty({0}, opts32);
+  Predicate pred{PRED_MASK, mask.data_ptr(), 0, 0.0};
+  return std::get<0>(compact(pred, n, opts32, nullptr));
 }
 
 torch::Tensor filter_cmp_scalar(torch::Tensor col, int64_t op, double scalar) {
   check_cuda(col, "col");
   int64_t n = col.numel();
-  if (n == 0) return torch::empty({0}, col.options().dtype(torch::kInt32));
-  auto st = cur_stream();
-  int nblocks = filter_grid(n);
-  auto counts = torch::empty({nblocks}, col.options().dtype(torch::kInt32));
+  auto opts32 = col.options().dtype(torch::kInt32);
+  if (n == 0) return torch::empty({0}, opts32);
   if (col.scalar_type() == torch::kInt32) col = col.to(torch::kInt64);
-  if (col.scalar_type() == torch::kFloat32) {
-    launch_filter_count_f32(col.data_ptr<float>(), n, (int)op, (float)scalar,
-                            counts.data_ptr<int32_t>(), st);
-  } else if (col.scalar_type() == torch::kInt64) {
-    launch_filter_count_i64(col.data_ptr<int64_t>(), n, (int)op,
-                            (int64_t)scalar, counts.data_ptr<int32_t>(), st);
-  } else {
-    TORCH_CHECK(false, "filter_cmp_scalar supports f32/i64/i32 cols");
-  }
-  auto [offs, total_t] = exscan(counts);
-  int64_t total = total_t.item<int32_t>();
-  auto out = torch::empty({total}, col.options().dtype(torch::kInt32));
-  if (total) {
-    if (col.scalar_type() == torch::kFloat32)
-      launch_filter_scatter_f32(col.data_ptr<float>(), n, (int)op,
-                                (float)scalar, offs.data_ptr<int32_t>(),
-                                out.data_ptr<int32_t>(), st);
-    else
-      launch_filter_scatter_i64(col.data_ptr<int64_t>(), n, (int)op,
-                                (int64_t)scalar, offs.data_ptr<int32_t>(),
-                                out.data_ptr<int32_t>(), st);
-  }
-  return out;
+  TORCH_CHECK(col.scalar_type() == torch::kFloat32 ||
+                  col.scalar_type() == torch::kInt64,
+              "filter_cmp_scalar supports f32/i64/i32 cols");
+  return std::get<0>(
+      compact(cmp_predicate(col, op, scalar), n, opts32, nullptr));
 }
 
 torch::Tensor gather(torch::Tensor col, torch::Tensor idx) {
@@ -705,30 +630,9 @@ torch::Tensor attention_qkv_bf16(torch::Tensor qkv, double scale,
 std::vector<torch::Tensor> gather_columns(std::vector<torch::Tensor> cols,
                                           torch::Tensor idx) {
   check_cuda(idx, "idx");
+  for (auto& c : cols) check_cuda(c, "col");
   auto idx32 = idx.scalar_type() == torch::kInt32 ? idx : idx.to(torch::kInt32);
-  int64_t m = idx32.numel();
-  std::vector<torch::Tensor> outs;
-  outs.reserve(cols.size());
-  std::vector<const void*> src;
-  std::vector<void*> dst;
-  std::vector<int> esz;
-  auto flush = [&]() {
-    if (!src.empty() && m > 0)
-      launch_gather_multi((int)src.size(), src.data(), dst.data(), esz.data(),
-                          idx32.data_ptr<int32_t>(), m, cur_stream());
-    src.clear(); dst.clear(); esz.clear();
-  };
-  for (auto& c : cols) {
-    check_cuda(c, "col");
-    auto out = torch::empty({m}, c.options());
-    outs.push_back(out);
-    src.push_back(c.data_ptr());
-    dst.push_back(out.data_ptr());
-    esz.push_back((int)c.element_size());
-    if ((int)src.size() == 32) flush();
-  }
-  flush();
-  return outs;
+  return gather_multi(cols, idx32, idx32.numel(), nullptr, {});
 }
 
 torch::Tensor radix_argsort(torch::Tensor keys, bool descending) {
@@ -810,62 +714,17 @@ std::tuple<std::vector<torch::Tensor>, int64_t> fused_filter_gather(
   auto col = cols[filter_idx];
   check_cuda(col, "filter col");
   int64_t n = col.numel();
-  auto st = cur_stream();
-  auto opts32 = col.options().dtype(torch::kInt32);
-  if (n == 0) {
-    std::vector<torch::Tensor> outs;
-    for (auto& c : cols) outs.push_back(torch::empty({0}, c.options()));
-    return {outs, 0};
+  torch::Tensor idx;
+  int64_t total = 0;
+  if (n > 0) {
+    if (col.scalar_type() != torch::kFloat32 &&
+        col.scalar_type() != torch::kInt64)
+      col = col.to(torch::kInt64);
+    std::tie(idx, total) =
+        compact(cmp_predicate(col, op, scalar), n,
+                col.options().dtype(torch::kInt32), nullptr);
   }
-  int nblocks = filter_grid(n);
-  auto counts = torch::empty({nblocks}, opts32);
-  bool is_f32 = col.scalar_type() == torch::kFloat32;
-  torch::Tensor col64;
-  if (!is_f32) {
-    col64 = col.scalar_type() == torch::kInt64 ? col : col.to(torch::kInt64);
-  }
-  if (is_f32)
-    launch_filter_count_f32(col.data_ptr<float>(), n, (int)op, (float)scalar,
-                            counts.data_ptr<int32_t>(), st);
-  else
-    launch_filter_count_i64(col64.data_ptr<int64_t>(), n, (int)op,
-                            (int64_t)scalar, counts.data_ptr<int32_t>(), st);
-  auto [offs, total_t] = exscan(counts);
-  int64_t total = total_t.item<int32_t>();  // the ONE host sync
-  auto idx = torch::empty({total}, opts32);
-  std::vector<torch::Tensor> outs;
-  outs.reserve(cols.size());
-  if (total) {
-    if (is_f32)
-      launch_filter_scatter_f32(col.data_ptr<float>(), n, (int)op,
-                                (float)scalar, offs.data_ptr<int32_t>(),
-                                idx.data_ptr<int32_t>(), st);
-    else
-      launch_filter_scatter_i64(col64.data_ptr<int64_t>(), n, (int)op,
-                                (int64_t)scalar, offs.data_ptr<int32_t>(),
-                                idx.data_ptr<int32_t>(), st);
-    std::vector<const void*> src;
-    std::vector<void*> dst;
-    std::vector<int> esz;
-    auto flush = [&]() {
-      if (!src.empty())
-        launch_gather_multi((int)src.size(), src.data(), dst.data(),
-                            esz.data(), idx.data_ptr<int32_t>(), total, st);
-      src.clear(); dst.clear(); esz.clear();
-    };
-    for (auto& c : cols) {
-      auto out = torch::empty({total}, c.options());
-      outs.push_back(out);
-      src.push_back(c.data_ptr());
-      dst.push_back(out.data_ptr());
-      esz.push_back((int)c.element_size());
-      if ((int)src.size() == 32) flush();
-    }
-    flush();
-  } else {
-    for (auto& c : cols) outs.push_back(torch::empty({0}, c.options()));
-  }
-  return {outs, total};
+  return {gather_multi(cols, idx, total, nullptr, {}), total};
 }
 
 // hipGraph-capturable variant of fused_filter_gather: writes compacted rows
@@ -883,61 +742,18 @@ void filter_gather_capture(std::vector<torch::Tensor> cols,
   auto col = cols[filter_idx];
   check_cuda(col, "filter col");
   int64_t n = col.numel();
-  auto st = cur_stream();
   TORCH_CHECK(n > 0, "capture path requires a non-empty static batch");
-  int nblocks = filter_grid(n);
-  auto counts = torch::empty({nblocks}, col.options().dtype(torch::kInt32));
-  bool is_f32 = col.scalar_type() == torch::kFloat32;
-  TORCH_CHECK(is_f32 || col.scalar_type() == torch::kInt64,
+  TORCH_CHECK(col.scalar_type() == torch::kFloat32 ||
+                  col.scalar_type() == torch::kInt64,
               "capture filter col must be f32 or i64");
-  if (is_f32)
-    launch_filter_count_f32(col.data_ptr<float>(), n, (int)op, (float)scalar,
-                            counts.data_ptr<int32_t>(), st);
-  else
-    launch_filter_count_i64(col.data_ptr<int64_t>(), n, (int)op,
-                            (int64_t)scalar, counts.data_ptr<int32_t>(), st);
-  torch::Tensor offs;
-  if (nblocks <= 1024) {
-    // single-block scan writes offsets AND the device total in one launch
-    // (replaces torch cumsum + sub + copy_ — 3 kernels → 1 in the graph)
-    offs = torch::empty({nblocks}, col.options().dtype(torch::kInt32));
-    launch_scan_counts(counts.data_ptr<int32_t>(), nblocks,
-                       offs.data_ptr<int32_t>(),
-                       count_out.data_ptr<int32_t>(), st);
-  } else {
-    auto [offs2, total_t] = exscan(counts);
-    offs = offs2;
-    count_out.copy_(total_t, /*non_blocking=*/true);
-  }
-  auto idx = torch::empty({n}, col.options().dtype(torch::kInt32));
-  if (is_f32)
-    launch_filter_scatter_f32(col.data_ptr<float>(), n, (int)op,
-                              (float)scalar, offs.data_ptr<int32_t>(),
-                              idx.data_ptr<int32_t>(), st);
-  else
-    launch_filter_scatter_i64(col.data_ptr<int64_t>(), n, (int)op,
-                              (int64_t)scalar, offs.data_ptr<int32_t>(),
-                              idx.data_ptr<int32_t>(), st);
-  std::vector<const void*> src;
-  std::vector<void*> dst;
-  std::vector<int> esz;
-  auto flush = [&]() {
-    if (!src.empty())
-      launch_gather_multi_dyn((int)src.size(), src.data(), dst.data(),
-                              esz.data(), idx.data_ptr<int32_t>(),
-                              count_out.data_ptr<int32_t>(), n, st);
-    src.clear(); dst.clear(); esz.clear();
-  };
-  for (size_t c = 0; c < cols.size(); ++c) {
+  for (size_t c = 0; c < cols.size(); ++c)
     TORCH_CHECK(outs[c].numel() >= n &&
                 outs[c].element_size() == cols[c].element_size(),
                 "out buffer too small or wrong dtype");
-    src.push_back(cols[c].data_ptr());
-    dst.push_back(outs[c].data_ptr());
-    esz.push_back((int)cols[c].element_size());
-    if ((int)src.size() == 32) flush();
-  }
-  flush();
+  auto idx = std::get<0>(compact(cmp_predicate(col, op, scalar), n,
+                                 col.options().dtype(torch::kInt32),
+                                 &count_out));
+  gather_multi(cols, idx, n, count_out.data_ptr<int32_t>(), outs);
 }
 
 // one-call `SELECT key, count(*), AGG(col)… FROM flow WHERE fcol OP lit

@@ -42,3 +42,33 @@ DEV_INLINE float float_unflip(uint32_t u) {
 }
 
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Free-slot marker of the open-addressing tables (GROUP BY and join).
+#define EMPTY_KEY 0x8000000000000000ll
+
+// Where a kernel's row count comes from. The sync form of an operator knows
+// it on the host; the capture form reads what an earlier kernel of the same
+// hipGraph wrote to device memory. Kernels take the type as a template
+// parameter, so both forms are instantiations of one body.
+struct HostCount {
+  int64_t n;
+  DEV_INLINE int64_t get() const { return n; }
+};
+struct DevCount {
+  const int32_t* __restrict__ n;
+  DEV_INLINE int64_t get() const { return *n; }
+};
+
+// Blocks of `block` threads covering n items, clamped to [1, cap]; kernels
+// launched with it are grid-stride.
+inline int capped_grid(int64_t n, int block = 256, int cap = 2048) {
+  int64_t g = (n + block - 1) / block;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
+template <typename T>
+__global__ void fill_kernel(T* p, T v, int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) p[i] = v;
+}

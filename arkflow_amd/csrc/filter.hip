@@ -5,6 +5,7 @@
 // block-count → scan → scatter keeps row order without global atomics;
 // the scan between passes is one tiny device cumsum done by the caller.
 #include "common.h"
+#include "relational_api.h"
 
 // items per block: 256 threads × 4 = 1024 rows — small batches (8192 rows)
 // still fill ≥8 blocks; big batches scale to thousands of workgroups.
@@ -26,17 +27,31 @@ DEV_INLINE bool cmp_apply(T v, int op, T s) {
   }
 }
 
-// ---- pass 1: per-block count of matching rows -------------------------------
+// ---- row predicates: does row i survive? ------------------------------------
 template <typename T>
-__global__ void filter_count_kernel(const T* __restrict__ col, int64_t n,
-                                    int op, T scalar,
-                                    int32_t* __restrict__ block_counts) {
+struct CmpPred {
+  const T* __restrict__ col;
+  int op;
+  T scalar;
+  DEV_INLINE bool operator()(int64_t i) const {
+    return cmp_apply(col[i], op, scalar);
+  }
+};
+struct MaskPred {
+  const bool* __restrict__ mask;
+  DEV_INLINE bool operator()(int64_t i) const { return mask[i]; }
+};
+
+// ---- pass 1: per-block count of matching rows -------------------------------
+template <typename Pred>
+__global__ void compact_count_kernel(Pred pred, int64_t n,
+                                     int32_t* __restrict__ block_counts) {
   int64_t base = (int64_t)blockIdx.x * FILTER_TILE;
   int cnt = 0;
 #pragma unroll
   for (int i = 0; i < FILTER_IPT; ++i) {
     int64_t idx = base + threadIdx.x + i * FILTER_BLOCK;
-    if (idx < n && cmp_apply(col[idx], op, scalar)) ++cnt;
+    if (idx < n && pred(idx)) ++cnt;
   }
   // wave reduce then LDS across the 4 waves
   __shared__ int wsum[FILTER_BLOCK / WAVE];
@@ -53,11 +68,10 @@ __global__ void filter_count_kernel(const T* __restrict__ col, int64_t n,
 }
 
 // ---- pass 2: scatter matching row indices at block offsets ------------------
-template <typename T>
-__global__ void filter_scatter_kernel(const T* __restrict__ col, int64_t n,
-                                      int op, T scalar,
-                                      const int32_t* __restrict__ block_offsets,
-                                      int32_t* __restrict__ out_idx) {
+template <typename Pred>
+__global__ void compact_scatter_kernel(
+    Pred pred, int64_t n, const int32_t* __restrict__ block_offsets,
+    int32_t* __restrict__ out_idx) {
   int64_t base = (int64_t)blockIdx.x * FILTER_TILE;
   __shared__ int wave_base[FILTER_BLOCK / WAVE + 1];
   int write = block_offsets[blockIdx.x];
@@ -67,8 +81,8 @@ __global__ void filter_scatter_kernel(const T* __restrict__ col, int64_t n,
 #pragma unroll
   for (int i = 0; i < FILTER_IPT; ++i) {
     int64_t idx = base + i * FILTER_BLOCK + threadIdx.x;
-    bool pred = (idx < n) && cmp_apply(col[idx], op, scalar);
-    uint64_t ballot = __ballot(pred);
+    bool keep = (idx < n) && pred(idx);
+    uint64_t ballot = __ballot(keep);
     int rank = __popcll(ballot & lanemask_lt());
     int wave_total = __popcll(ballot);
     if (lane == 0) wave_base[wid + 1] = wave_total;
@@ -79,65 +93,57 @@ __global__ void filter_scatter_kernel(const T* __restrict__ col, int64_t n,
         wave_base[w] += wave_base[w - 1];
     }
     __syncthreads();
-    if (pred) out_idx[wave_base[wid] + rank] = (int32_t)idx;
+    if (keep) out_idx[wave_base[wid] + rank] = (int32_t)idx;
     write = wave_base[FILTER_BLOCK / WAVE];
     __syncthreads();
   }
 }
 
-// ---- mask (bool) variants ---------------------------------------------------
-__global__ void mask_count_kernel(const bool* __restrict__ mask, int64_t n,
-                                  int32_t* __restrict__ block_counts) {
-  int64_t base = (int64_t)blockIdx.x * FILTER_TILE;
-  int cnt = 0;
-#pragma unroll
-  for (int i = 0; i < FILTER_IPT; ++i) {
-    int64_t idx = base + threadIdx.x + i * FILTER_BLOCK;
-    if (idx < n && mask[idx]) ++cnt;
-  }
-  __shared__ int wsum[FILTER_BLOCK / WAVE];
-  int v = cnt;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int total = 0;
-#pragma unroll
-    for (int w = 0; w < FILTER_BLOCK / WAVE; ++w) total += wsum[w];
-    block_counts[blockIdx.x] = total;
+// Calls f with the device functor for a host-side Predicate.
+template <typename F>
+static void with_pred(const Predicate& p, F&& f) {
+  switch (p.kind) {
+    case PRED_MASK: f(MaskPred{(const bool*)p.data}); break;
+    case PRED_F32:
+      f(CmpPred<float>{(const float*)p.data, p.op, (float)p.scalar}); break;
+    case PRED_I64:
+      f(CmpPred<int64_t>{(const int64_t*)p.data, p.op, (int64_t)p.scalar});
+      break;
   }
 }
 
-__global__ void mask_scatter_kernel(const bool* __restrict__ mask, int64_t n,
-                                    const int32_t* __restrict__ block_offsets,
-                                    int32_t* __restrict__ out_idx) {
-  int64_t base = (int64_t)blockIdx.x * FILTER_TILE;
-  __shared__ int wave_base[FILTER_BLOCK / WAVE + 1];
-  int write = block_offsets[blockIdx.x];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < FILTER_IPT; ++i) {
-    int64_t idx = base + i * FILTER_BLOCK + threadIdx.x;
-    bool pred = (idx < n) && mask[idx];
-    uint64_t ballot = __ballot(pred);
-    int rank = __popcll(ballot & lanemask_lt());
-    int wave_total = __popcll(ballot);
-    if (lane == 0) wave_base[wid + 1] = wave_total;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      wave_base[0] = write;
-      for (int w = 1; w <= FILTER_BLOCK / WAVE; ++w)
-        wave_base[w] += wave_base[w - 1];
-    }
-    __syncthreads();
-    if (pred) out_idx[wave_base[wid] + rank] = (int32_t)idx;
-    write = wave_base[FILTER_BLOCK / WAVE];
-    __syncthreads();
-  }
+extern "C" int filter_grid(int64_t n) {
+  return (int)((n + FILTER_TILE - 1) / FILTER_TILE);
+}
+
+extern "C" void launch_compact_count(const Predicate* pred, int64_t n,
+                                     int32_t* counts, hipStream_t st) {
+  with_pred(*pred, [&](auto p) {
+    compact_count_kernel<<<filter_grid(n), FILTER_BLOCK, 0, st>>>(p, n, counts);
+  });
+}
+extern "C" void launch_compact_scatter(const Predicate* pred, int64_t n,
+                                       const int32_t* offs, int32_t* out_idx,
+                                       hipStream_t st) {
+  with_pred(*pred, [&](auto p) {
+    compact_scatter_kernel<<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
+        p, n, offs, out_idx);
+  });
 }
 
 // ---- gather -----------------------------------------------------------------
+// Columns are gathered as opaque 1/2/4/8-byte elements: calls f with a zero
+// of the unsigned type of that width.
+template <typename F>
+__host__ __device__ __forceinline__ void with_elem_type(int esz, F&& f) {
+  switch (esz) {
+    case 1: f(uint8_t{}); break;
+    case 2: f(uint16_t{}); break;
+    case 4: f(uint32_t{}); break;
+    default: f(uint64_t{}); break;
+  }
+}
+
 // Coalesced row gather by element size; one thread per output row × chunk.
 template <typename T>
 __global__ void gather_kernel(const T* __restrict__ src,
@@ -148,61 +154,15 @@ __global__ void gather_kernel(const T* __restrict__ src,
   for (; i < m; i += stride) dst[i] = src[idx[i]];
 }
 
-// ---- host-visible launchers (called from bindings.cpp) ----------------------
-extern "C" {
-
-int filter_grid(int64_t n) { return (int)((n + FILTER_TILE - 1) / FILTER_TILE); }
-
-void launch_filter_count_f32(const float* col, int64_t n, int op, float s,
-                             int32_t* counts, hipStream_t st) {
-  filter_count_kernel<float><<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
-      col, n, op, s, counts);
+extern "C" void launch_gather(const void* src, const int32_t* idx, int64_t m,
+                              void* dst, int elem_size, hipStream_t st) {
+  if (m < 1) return;
+  with_elem_type(elem_size, [&](auto t) {
+    using T = decltype(t);
+    gather_kernel<T><<<capped_grid(m), 256, 0, st>>>((const T*)src, idx, m,
+                                                     (T*)dst);
+  });
 }
-void launch_filter_scatter_f32(const float* col, int64_t n, int op, float s,
-                               const int32_t* offs, int32_t* out,
-                               hipStream_t st) {
-  filter_scatter_kernel<float><<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
-      col, n, op, s, offs, out);
-}
-void launch_filter_count_i64(const int64_t* col, int64_t n, int op, int64_t s,
-                             int32_t* counts, hipStream_t st) {
-  filter_count_kernel<int64_t><<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
-      col, n, op, s, counts);
-}
-void launch_filter_scatter_i64(const int64_t* col, int64_t n, int op,
-                               int64_t s, const int32_t* offs, int32_t* out,
-                               hipStream_t st) {
-  filter_scatter_kernel<int64_t><<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
-      col, n, op, s, offs, out);
-}
-void launch_mask_count(const bool* mask, int64_t n, int32_t* counts,
-                       hipStream_t st) {
-  mask_count_kernel<<<filter_grid(n), FILTER_BLOCK, 0, st>>>(mask, n, counts);
-}
-void launch_mask_scatter(const bool* mask, int64_t n, const int32_t* offs,
-                         int32_t* out, hipStream_t st) {
-  mask_scatter_kernel<<<filter_grid(n), FILTER_BLOCK, 0, st>>>(
-      mask, n, offs, out);
-}
-
-void launch_gather(const void* src, const int32_t* idx, int64_t m,
-                   void* dst, int elem_size, hipStream_t st) {
-  int grid = (int)((m + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid == 0) return;
-  switch (elem_size) {
-    case 1: gather_kernel<uint8_t><<<grid, 256, 0, st>>>(
-        (const uint8_t*)src, idx, m, (uint8_t*)dst); break;
-    case 2: gather_kernel<uint16_t><<<grid, 256, 0, st>>>(
-        (const uint16_t*)src, idx, m, (uint16_t*)dst); break;
-    case 4: gather_kernel<uint32_t><<<grid, 256, 0, st>>>(
-        (const uint32_t*)src, idx, m, (uint32_t*)dst); break;
-    default: gather_kernel<uint64_t><<<grid, 256, 0, st>>>(
-        (const uint64_t*)src, idx, m, (uint64_t*)dst); break;
-  }
-}
-
-}  // extern "C"
 
 // ---- multi-column gather: one launch for a whole batch ----------------------
 #define GATHER_MAX_COLS 32
@@ -213,9 +173,15 @@ struct GatherSpec {
   int esz[GATHER_MAX_COLS];
 };
 
+// Count = HostCount: m rows. Count = DevCount: the row count lives in DEVICE
+// memory (written by the scan), so the whole filter→gather chain captures
+// into a hipGraph with no host sync; the grid is sized for the batch cap and
+// threads past the count exit.
+template <typename Count>
 __global__ void gather_multi_kernel(GatherSpec spec,
                                     const int32_t* __restrict__ idx,
-                                    int64_t m) {
+                                    Count count) {
+  int64_t m = count.get();
   int64_t total = (int64_t)spec.ncols * m;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -223,22 +189,17 @@ __global__ void gather_multi_kernel(GatherSpec spec,
     int c = (int)(i / m);
     int64_t j = i - (int64_t)c * m;
     int64_t s = idx[j];
-    switch (spec.esz[c]) {
-      case 1: ((uint8_t*)spec.dst[c])[j] = ((const uint8_t*)spec.src[c])[s];
-              break;
-      case 2: ((uint16_t*)spec.dst[c])[j] = ((const uint16_t*)spec.src[c])[s];
-              break;
-      case 4: ((uint32_t*)spec.dst[c])[j] = ((const uint32_t*)spec.src[c])[s];
-              break;
-      default: ((uint64_t*)spec.dst[c])[j] = ((const uint64_t*)spec.src[c])[s];
-               break;
-    }
+    with_elem_type(spec.esz[c], [&](auto t) {
+      using T = decltype(t);
+      ((T*)spec.dst[c])[j] = ((const T*)spec.src[c])[s];
+    });
   }
 }
 
-extern "C" void launch_gather_multi(int ncols, const void** src, void** dst,
-                                    const int* esz, const int32_t* idx,
-                                    int64_t m, hipStream_t st) {
+extern "C" void launch_gather_multi(int ncols, const void* const* src,
+                                    void* const* dst, const int* esz,
+                                    const int32_t* idx, int64_t m,
+                                    const int32_t* count_dev, hipStream_t st) {
   GatherSpec spec{};
   spec.ncols = ncols;
   for (int c = 0; c < ncols; ++c) {
@@ -247,59 +208,12 @@ extern "C" void launch_gather_multi(int ncols, const void** src, void** dst,
     spec.esz[c] = esz[c];
   }
   int64_t total = (int64_t)ncols * m;
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) return;
-  gather_multi_kernel<<<grid, 256, 0, st>>>(spec, idx, m);
-}
-
-// ---- dyn-count multi-gather: hipGraph-capturable compaction tail ------------
-// Same as gather_multi_kernel but the row count lives in DEVICE memory
-// (written by the scan), so the whole filter→gather chain captures into a
-// hipGraph with no host sync. Launched with a grid sized for the batch cap;
-// threads past *count_dev exit.
-__global__ void gather_multi_dyn_kernel(GatherSpec spec,
-                                        const int32_t* __restrict__ idx,
-                                        const int32_t* __restrict__ count_dev,
-                                        int64_t cap) {
-  int64_t m = (int64_t)*count_dev;
-  int64_t total = (int64_t)spec.ncols * m;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int c = (int)(i / m);
-    int64_t j = i - (int64_t)c * m;
-    int64_t s = idx[j];
-    switch (spec.esz[c]) {
-      case 1: ((uint8_t*)spec.dst[c])[j] = ((const uint8_t*)spec.src[c])[s];
-              break;
-      case 2: ((uint16_t*)spec.dst[c])[j] = ((const uint16_t*)spec.src[c])[s];
-              break;
-      case 4: ((uint32_t*)spec.dst[c])[j] = ((const uint32_t*)spec.src[c])[s];
-              break;
-      default: ((uint64_t*)spec.dst[c])[j] = ((const uint64_t*)spec.src[c])[s];
-               break;
-    }
-  }
-}
-
-extern "C" void launch_gather_multi_dyn(int ncols, const void** src,
-                                        void** dst, const int* esz,
-                                        const int32_t* idx,
-                                        const int32_t* count_dev, int64_t cap,
-                                        hipStream_t st) {
-  GatherSpec spec{};
-  spec.ncols = ncols;
-  for (int c = 0; c < ncols; ++c) {
-    spec.src[c] = src[c];
-    spec.dst[c] = dst[c];
-    spec.esz[c] = esz[c];
-  }
-  int64_t total = (int64_t)ncols * cap;
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) return;
-  gather_multi_dyn_kernel<<<grid, 256, 0, st>>>(spec, idx, count_dev, cap);
+  if (total < 1) return;
+  int grid = capped_grid(total, 256, 4096);
+  if (count_dev)
+    gather_multi_kernel<<<grid, 256, 0, st>>>(spec, idx, DevCount{count_dev});
+  else
+    gather_multi_kernel<<<grid, 256, 0, st>>>(spec, idx, HostCount{m});
 }
 
 // ---- per-row bytes hash (binary columns: group-by / repartition keys) -------
@@ -323,10 +237,8 @@ __global__ void bytes_hash_kernel(const uint8_t* __restrict__ data,
 
 extern "C" void launch_bytes_hash(const uint8_t* data, const int64_t* offsets,
                                   int64_t n, int64_t* out, hipStream_t st) {
-  int grid = (int)((n + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) return;
-  bytes_hash_kernel<<<grid, 256, 0, st>>>(data, offsets, n, out);
+  if (n < 1) return;
+  bytes_hash_kernel<<<capped_grid(n), 256, 0, st>>>(data, offsets, n, out);
 }
 
 // ------------------------------------------------------------------ prefix sum
@@ -490,8 +402,7 @@ extern "C" void launch_bytes_match(const uint8_t* data, const int64_t* offsets,
   nd.len = nl > MATCH_MAX_NEEDLE ? MATCH_MAX_NEEDLE : nl;
   nd.mode = mode;
   for (int k = 0; k < nd.len; ++k) nd.bytes[k] = needle[k];
-  int grid = (int)((n + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) return;
-  bytes_match_kernel<<<grid, 256, 0, st>>>(data, offsets, n, nd, out);
+  if (n < 1) return;
+  bytes_match_kernel<<<capped_grid(n), 256, 0, st>>>(data, offsets, n, nd,
+                                                     out);
 }

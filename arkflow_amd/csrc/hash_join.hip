@@ -6,8 +6,8 @@
 // per-row `next` array (chaining handles duplicate keys). Probe = two passes
 // (count → scan by caller → emit) so output pairs are dense and left-ordered.
 #include "common.h"
+#include "relational_api.h"
 
-#define EMPTY_KEY 0x8000000000000000ll
 #define JOIN_BLOCK 256
 
 __global__ void join_build_kernel(const int64_t* __restrict__ keys, int64_t n,
@@ -99,32 +99,16 @@ __global__ void join_probe_emit_kernel(const int64_t* __restrict__ lkeys,
   }
 }
 
-__global__ void join_fill_kernel(int64_t* p, int64_t v, int64_t n) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) p[i] = v;  // grid-stride: grid capped at 2048
-}
-__global__ void join_fill32_kernel(int32_t* p, int32_t v, int64_t n) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) p[i] = v;
-}
-
 extern "C" {
-
-static int jgrid(int64_t n) {
-  int64_t g = (n + JOIN_BLOCK - 1) / JOIN_BLOCK;
-  return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
 
 void launch_join_build(const int64_t* rkeys, int64_t n_right,
                        int64_t* table_keys, int32_t* table_head, int32_t* next,
                        uint32_t table_size, hipStream_t st) {
-  join_fill_kernel<<<jgrid(table_size), JOIN_BLOCK, 0, st>>>(
+  fill_kernel<int64_t><<<capped_grid(table_size), JOIN_BLOCK, 0, st>>>(
       table_keys, EMPTY_KEY, table_size);
-  join_fill32_kernel<<<jgrid(table_size), JOIN_BLOCK, 0, st>>>(
+  fill_kernel<int32_t><<<capped_grid(table_size), JOIN_BLOCK, 0, st>>>(
       table_head, -1, table_size);
-  join_build_kernel<<<jgrid(n_right), JOIN_BLOCK, 0, st>>>(
+  join_build_kernel<<<capped_grid(n_right), JOIN_BLOCK, 0, st>>>(
       rkeys, n_right, table_keys, table_head, next, table_size - 1);
 }
 
@@ -133,7 +117,7 @@ void launch_join_probe_count(const int64_t* lkeys, int64_t n_left,
                              const int32_t* table_head, const int32_t* next,
                              const int64_t* rkeys, uint32_t table_size,
                              int32_t* counts, hipStream_t st) {
-  join_probe_count_kernel<<<jgrid(n_left), JOIN_BLOCK, 0, st>>>(
+  join_probe_count_kernel<<<capped_grid(n_left), JOIN_BLOCK, 0, st>>>(
       lkeys, n_left, table_keys, table_head, next, rkeys, table_size - 1,
       counts);
 }
@@ -144,7 +128,7 @@ void launch_join_probe_emit(const int64_t* lkeys, int64_t n_left,
                             const int64_t* rkeys, uint32_t table_size,
                             const int32_t* offsets, int64_t* l_out,
                             int64_t* r_out, hipStream_t st) {
-  join_probe_emit_kernel<<<jgrid(n_left), JOIN_BLOCK, 0, st>>>(
+  join_probe_emit_kernel<<<capped_grid(n_left), JOIN_BLOCK, 0, st>>>(
       lkeys, n_left, table_keys, table_head, next, rkeys, table_size - 1,
       offsets, l_out, r_out);
 }

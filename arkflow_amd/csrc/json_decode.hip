@@ -5,6 +5,7 @@
 // kernel covers the configured-schema hot path: flat JSON, numeric/bool
 // fields, other keys skipped including nested objects/arrays/strings).
 #include "common.h"
+#include "kernels_api.h"
 
 #define JSON_MAX_FIELDS 16
 #define JSON_MAX_NAME 24

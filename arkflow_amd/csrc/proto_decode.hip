@@ -6,6 +6,7 @@
 // protobuf.rs — scalar proto3 only). String fields are skipped here (host
 // path handles them); numeric-only schemas stay fully on-device.
 #include "common.h"
+#include "kernels_api.h"
 
 #define PROTO_MAX_FIELDS 16
 

@@ -1,0 +1,107 @@
+// Host-side interface of the relational kernels (WHERE, gather, GROUP BY,
+// join, ORDER BY and the scans between their passes). Included by the .hip
+// file that defines each launcher and by bindings.cpp, so a declaration that
+// drifts from its definition is a compile error.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// Row predicate of a stream compaction: a bool mask, or `col OP scalar` on an
+// f32 / i64 column. op: 0 < 1 <= 2 > 3 >= 4 == 5 != ; scalar is cast to the
+// column's type.
+enum PredKind { PRED_MASK = 0, PRED_F32 = 1, PRED_I64 = 2 };
+struct Predicate {
+  PredKind kind;
+  const void* data;  // bool[n], float[n] or int64_t[n]
+  int op;
+  double scalar;
+};
+
+extern "C" {
+
+// ---- filter.hip: compaction, gather -----------------------------------------
+int filter_grid(int64_t n);  // blocks (= entries of counts / offs) for n rows
+void launch_compact_count(const Predicate* pred, int64_t n, int32_t* counts,
+                          hipStream_t st);
+void launch_compact_scatter(const Predicate* pred, int64_t n,
+                            const int32_t* offs, int32_t* out_idx,
+                            hipStream_t st);
+void launch_gather(const void* src, const int32_t* idx, int64_t m, void* dst,
+                   int elem_size, hipStream_t st);
+// Up to 32 columns in one launch. count_dev null: m rows. Otherwise the row
+// count is read from *count_dev on the device and m only sizes the grid.
+void launch_gather_multi(int ncols, const void* const* src, void* const* dst,
+                         const int* esz, const int32_t* idx, int64_t m,
+                         const int32_t* count_dev, hipStream_t st);
+
+// ---- filter.hip: binary columns, prefix sum ---------------------------------
+void launch_bytes_hash(const uint8_t* data, const int64_t* offsets, int64_t n,
+                       int64_t* out, hipStream_t st);
+void launch_bytes_match(const uint8_t* data, const int64_t* offsets, int64_t n,
+                        const uint8_t* needle, int nl, int mode, bool* out,
+                        hipStream_t st);
+int scan_grid(int64_t n);
+void launch_scan_partials(const int32_t* in, int64_t n, int64_t* partials,
+                          hipStream_t st);
+void launch_scan_boffs64(const int64_t* partials, int nb, int64_t* boffs,
+                         int64_t* total_out, hipStream_t st);
+void launch_scan_write(const int32_t* in, int64_t n, const int64_t* block_offs,
+                       int64_t* out, hipStream_t st);
+
+// ---- hash_agg.hip -----------------------------------------------------------
+void launch_hash_build(const int64_t* keys, int64_t n, int64_t* table_keys,
+                       int32_t* table_gids, uint32_t table_size,
+                       int32_t* counter, int32_t* gids_out, hipStream_t st);
+void launch_hash_export(const int64_t* table_keys, const int32_t* table_gids,
+                        uint32_t table_size, int64_t* uniq, hipStream_t st);
+void launch_segment_reduce_f32(const float* vals, const int32_t* gids,
+                               int64_t n, int g, int op, float* out,
+                               int32_t* scratch_flipped, hipStream_t st);
+void launch_hash_agg_capture(const int64_t* keys, const int32_t* nrow,
+                             int64_t n_cap, int64_t* table_keys,
+                             int32_t* table_gids, uint32_t table_size,
+                             int32_t* counter, int32_t* gids, float* counts,
+                             int g_cap, const float* const* vals,
+                             const int* ops, float* const* red_out,
+                             int32_t* const* mm_scratch, int nv,
+                             int64_t* uniq, int64_t* counts_i64,
+                             int32_t* gcount_out, hipStream_t st);
+
+// ---- hash_join.hip ----------------------------------------------------------
+void launch_join_build(const int64_t* rkeys, int64_t n_right,
+                       int64_t* table_keys, int32_t* table_head, int32_t* next,
+                       uint32_t table_size, hipStream_t st);
+void launch_join_probe_count(const int64_t* lkeys, int64_t n_left,
+                             const int64_t* table_keys,
+                             const int32_t* table_head, const int32_t* next,
+                             const int64_t* rkeys, uint32_t table_size,
+                             int32_t* counts, hipStream_t st);
+void launch_join_probe_emit(const int64_t* lkeys, int64_t n_left,
+                            const int64_t* table_keys,
+                            const int32_t* table_head, const int32_t* next,
+                            const int64_t* rkeys, uint32_t table_size,
+                            const int32_t* offsets, int64_t* l_out,
+                            int64_t* r_out, hipStream_t st);
+
+// ---- radix_sort.hip ---------------------------------------------------------
+void launch_f32_to_ordered(const float* in, uint32_t* out, int64_t n,
+                           int descending, hipStream_t st);
+void launch_i32_to_ordered(const int32_t* in, uint32_t* out, int64_t n,
+                           int descending, hipStream_t st);
+void launch_i64_to_ordered(const int64_t* in, uint64_t* out, int64_t n,
+                           int descending, hipStream_t st);
+int onesweep_nblocks(int64_t n);
+void launch_os_hist256_u32(const uint32_t* keys, int64_t n, int shift,
+                           int32_t* hist, int nblocks, hipStream_t st);
+void launch_os_hist256_u64(const uint64_t* keys, int64_t n, int shift,
+                           int32_t* hist, int nblocks, hipStream_t st);
+void launch_onesweep_pass_u32(const uint32_t* keys_in, const int32_t* idx_in,
+                              uint32_t* keys_out, int32_t* idx_out, int64_t n,
+                              int shift, const int32_t* block_offsets,
+                              int nblocks, hipStream_t st);
+void launch_onesweep_pass_u64(const uint64_t* keys_in, const int32_t* idx_in,
+                              uint64_t* keys_out, int32_t* idx_out, int64_t n,
+                              int shift, const int32_t* block_offsets,
+                              int nblocks, hipStream_t st);
+
+}  // extern "C"

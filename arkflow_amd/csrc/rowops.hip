@@ -2,6 +2,7 @@
 // fused residual add) and row softmax. Memory-bound → vectorized short4/short8
 // loads per guide Guideline 13; one block per row, wave+LDS reductions.
 #include "gemm_common.h"  // Act / apply_act: the GEMM epilogues' formula
+#include "kernels_api.h"
 
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(8))) __bf16 vbf16x8;

@@ -15,6 +15,7 @@
 //   gemv_bf16_f32   [M,K]·[K] + bias → f32 scores (replaces the final
 //                   hipBLASLt N=1 GEMM + the bf16→f32 copy)
 #include "common.h"
+#include "kernels_api.h"
 
 // counter-based RNG: mix64(ctr ^ element-id) — statistical quality is ample
 // for synthetic benchmark data (uniform floats / uniform ints).

@@ -1290,3 +1290,169 @@ def test_left_join_residual_anti_join_on_gpu(dev):
     ).execute({"flow": flow, "dims": dims})
     got = r.column("a").data.cpu().tolist()
     assert got == [x for x in range(20) if x % 5 >= 2]
+
+
+# ---- relational kernels: tile/wave edges, 32-column flush, device counts ----
+EDGE_NS = (1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4097)
+MIXED_DTYPES = (torch.uint8, torch.bfloat16, torch.float32, torch.int64)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.int64, torch.int32])
+def test_compaction_tile_and_wave_edges(nat, dev, dtype):
+    """mask_to_indices / filter_cmp_scalar at every wave (64), strip (256)
+    and tile (1024) edge, keeping none, all and about half of the rows."""
+    torch.manual_seed(60)
+    for n in EDGE_NS:
+        col = torch.randint(0, 100, (n,), device=dev).to(dtype)
+        # (op, scalar): GE 50 keeps ~half, GE 0 keeps all, LT 0 keeps none
+        for op_i, op_fn, s in ((3, torch.ge, 50.0), (3, torch.ge, 0.0),
+                               (0, torch.lt, 0.0)):
+            mask = op_fn(col, s)
+            exp = torch.nonzero(mask).flatten().to(torch.int32)
+            got = nat.filter_cmp_scalar(col, op_i, s)
+            assert got.dtype == torch.int32
+            assert torch.equal(got, exp), f"cmp n={n} op={op_i} s={s}"
+            got_m = nat.mask_to_indices(mask)
+            assert got_m.dtype == torch.int32
+            assert torch.equal(got_m, exp), f"mask n={n} op={op_i} s={s}"
+
+
+def _mixed_cols(ncols, n, dev):
+    # column 2 (f32) is the filter column of the tests below
+    return [(torch.rand(n, device=dev) * 100).to(MIXED_DTYPES[c % 4])
+            for c in range(ncols)]
+
+
+@pytest.mark.parametrize("ncols", [33, 65])
+def test_gather_past_32_column_flush(nat, dev, ncols):
+    """More columns than one multi-gather launch holds (32), mixed element
+    sizes, through all three callers of the multi-column gather."""
+    torch.manual_seed(61)
+    n = 1000
+    cols = _mixed_cols(ncols, n, dev)
+    idx = torch.randint(0, n, (777,), device=dev, dtype=torch.int32)
+    got = nat.gather_columns(cols, idx)
+    assert len(got) == ncols
+    for c, g in zip(cols, got):
+        assert g.dtype == c.dtype and torch.equal(g, c[idx.long()])
+    empty = nat.gather_columns(cols, idx[:0])
+    assert len(empty) == ncols
+    for c, g in zip(cols, empty):
+        assert g.dtype == c.dtype and g.shape == (0,)
+
+    mask = cols[2] >= 40.0
+    outs, total = nat.fused_filter_gather(cols, 2, 3, 40.0)
+    assert total == int(mask.sum()) and len(outs) == ncols
+    for c, o in zip(cols, outs):
+        assert o.dtype == c.dtype and torch.equal(o, c[mask])
+
+    bufs = [torch.full((n,), 77, device=dev, dtype=c.dtype) for c in cols]
+    count = torch.zeros(1, device=dev, dtype=torch.int32)
+    nat.filter_gather_capture(cols, 2, 3, 40.0, bufs, count)
+    assert int(count.item()) == total
+    for c, b, o in zip(cols, bufs, outs):
+        assert torch.equal(b[:total], o)
+        assert torch.equal(b[total:], torch.full_like(b[total:], 77))
+
+
+@pytest.mark.parametrize("case", ["i64_col", "torch_scan", "keep_none"])
+def test_filter_gather_capture_cases(nat, dev, case):
+    """i64 filter column, >1024 blocks (torch exscan instead of the
+    single-block scan), and a predicate keeping nothing — against
+    fused_filter_gather; rows of outs past count stay untouched."""
+    torch.manual_seed(62)
+    if case == "i64_col":
+        n, fidx, op, s = 5000, 1, 3, 50.0
+    elif case == "torch_scan":
+        n, fidx, op, s = 1024 * 1024 + 1, 0, 3, 0.5  # 1025 blocks
+    else:
+        n, fidx, op, s = 5000, 0, 0, -1.0            # f0 < -1: no row
+    cols = [torch.rand(n, device=dev),
+            torch.randint(0, 100, (n,), device=dev, dtype=torch.int64),
+            torch.randn(n, device=dev)]
+    outs = [torch.full((n,), -7, device=dev, dtype=c.dtype) for c in cols]
+    count = torch.full((1,), -1, device=dev, dtype=torch.int32)
+    nat.filter_gather_capture(cols, fidx, op, s, outs, count)
+    ref_outs, ref_total = nat.fused_filter_gather(cols, fidx, op, s)
+    kept = int(count.item())
+    assert kept == ref_total
+    assert (kept == 0) == (case == "keep_none")
+    for o, r in zip(outs, ref_outs):
+        assert torch.equal(o[:kept], r)
+        assert torch.equal(o[kept:], torch.full_like(o[kept:], -7))
+
+
+def test_hash_agg_capture_respects_device_row_count(nat, dev):
+    """hash_agg_capture on padded inputs: rows past nrow hold keys that occur
+    nowhere before it, so a kernel ignoring nrow yields extra groups."""
+    torch.manual_seed(63)
+    n_cap, nrow = 4096, 3000
+    keys = torch.randint(0, 57, (n_cap,), device=dev, dtype=torch.int64)
+    keys[nrow:] = torch.randint(1000, 1100, (n_cap - nrow,), device=dev)
+    f0 = torch.rand(n_cap, device=dev)
+    f1 = torch.randn(n_cap, device=dev) * 5
+    nrow_t = torch.tensor([nrow], device=dev, dtype=torch.int32)
+    gcount = torch.full((1,), -1, device=dev, dtype=torch.int32)
+    uniq, cnt, red = nat.hash_agg_capture(keys, nrow_t, [f0, f1, f1],
+                                          [0, 1, 2], 256, 128, gcount)
+    uniq_ref, inv = torch.unique(keys[:nrow], return_inverse=True)
+    g = uniq_ref.numel()
+    assert int(gcount.item()) == g
+    cnt_ref = torch.bincount(inv, minlength=g)
+    sum_ref = torch.zeros(g, dtype=torch.float64, device=dev)
+    sum_ref.index_add_(0, inv, f0[:nrow].double())
+    mn_ref = torch.full((g,), float("inf"), device=dev)
+    mn_ref.scatter_reduce_(0, inv, f1[:nrow], "amin", include_self=True)
+    mx_ref = torch.full((g,), float("-inf"), device=dev)
+    mx_ref.scatter_reduce_(0, inv, f1[:nrow], "amax", include_self=True)
+    order = torch.argsort(uniq[:g])
+    assert torch.equal(uniq[:g][order], uniq_ref)
+    assert torch.equal(cnt[:g][order], cnt_ref)
+    assert torch.allclose(red[0][:g][order].double(), sum_ref, rtol=1e-4)
+    assert torch.equal(red[1][:g][order], mn_ref)
+    assert torch.equal(red[2][:g][order], mx_ref)
+
+    nrow_t.zero_()
+    gcount.fill_(-1)
+    nat.hash_agg_capture(keys, nrow_t, [f0, f1, f1], [0, 1, 2], 256, 128,
+                         gcount)
+    assert int(gcount.item()) == 0
+
+
+@pytest.mark.parametrize("g", [2048, 2049])
+def test_segment_reduce_lds_global_boundary(nat, dev, g):
+    """g = 2048 is the last LDS-tiled group count, 2049 the first on the
+    global-atomic kernels."""
+    torch.manual_seed(64)
+    n = 20_000
+    gids = torch.randint(0, g, (n,), device=dev, dtype=torch.int32)
+    vals = torch.randn(n, device=dev) * 10
+    exp_sum = torch.zeros(g, device=dev).scatter_add_(0, gids.long(), vals)
+    got_sum = nat.segment_reduce_f32(vals, gids, g, 0)
+    assert torch.allclose(got_sum, exp_sum, atol=1e-2, rtol=1e-4)
+    exp_min = torch.full((g,), float("inf"), device=dev).scatter_reduce_(
+        0, gids.long(), vals, reduce="amin")
+    assert torch.equal(nat.segment_reduce_f32(vals, gids, g, 1), exp_min)
+    exp_max = torch.full((g,), float("-inf"), device=dev).scatter_reduce_(
+        0, gids.long(), vals, reduce="amax")
+    assert torch.equal(nat.segment_reduce_f32(vals, gids, g, 2), exp_max)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_hash_group_and_join_small(nat, dev, n):
+    torch.manual_seed(65)
+    keys = torch.randint(-20, 20, (n,), device=dev, dtype=torch.int64)
+    gid, uniq = nat.hash_group_i64(keys)
+    assert uniq.shape[0] == torch.unique(keys).shape[0]
+    assert torch.equal(uniq[gid.long()], keys)
+    assert int(gid.max()) == uniq.shape[0] - 1 and int(gid.min()) == 0
+
+    import collections
+    rk = torch.randint(-20, 20, (n,), device=dev, dtype=torch.int64)
+    for lk in (keys, rk):  # random pairing, then a side joined with itself
+        l_idx, r_idx = nat.join_inner_i64(lk, rk)
+        assert torch.equal(lk[l_idx], rk[r_idx])
+        rc = collections.Counter(rk.cpu().tolist())
+        assert l_idx.shape[0] == sum(rc[k] for k in lk.cpu().tolist())
+        pair = l_idx * n + r_idx
+        assert torch.unique(pair).shape[0] == pair.shape[0]
