@@ -588,8 +588,24 @@ torch::Tensor bias_act_bf16(torch::Tensor x,
   return out;
 }
 
+// Valid-length argument of the attention bindings: absent, or an int32 [B]
+// contiguous device tensor. Checked before any launch; its VALUES are never
+// read on the host (no sync, capturable) — the kernels clamp them to [0, S].
+static bool check_lens(const c10::optional<torch::Tensor>& lens, int64_t B,
+                       const torch::Tensor& like) {
+  if (!lens.has_value() || !lens->defined()) return false;
+  TORCH_CHECK(lens->is_cuda() && lens->device() == like.device(),
+              "lens must be on the inputs' device");
+  TORCH_CHECK(lens->scalar_type() == torch::kInt32, "lens must be int32");
+  TORCH_CHECK(lens->dim() == 1 && lens->size(0) == B,
+              "lens must be 1-D of length B=", B);
+  TORCH_CHECK(lens->is_contiguous(), "lens must be contiguous");
+  return true;
+}
+
 torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                             double scale) {
+                             double scale,
+                             c10::optional<torch::Tensor> lens) {
   check_cuda(q, "q");
   check_cuda(k, "k");
   check_cuda(v, "v");
@@ -601,10 +617,16 @@ torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
               "k and v must match q's shape");
   int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+  // the packed layout is BH independent rows: one length per (b, h)
+  torch::Tensor lens_bh;
+  if (check_lens(lens, B, q))
+    lens_bh = H == 1 ? *lens : lens->repeat_interleave(H).contiguous();
   auto out = torch::empty_like(q);
-  int rc = launch_attention_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                 out.data_ptr(), (int)(B * H), (int)S, (int)D,
-                                 (float)scale, cur_stream());
+  int rc = launch_attention_bf16(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)(B * H),
+      (int)S, (int)D, (float)scale,
+      lens_bh.defined() ? lens_bh.data_ptr<int32_t>() : nullptr,
+      cur_stream());
   TORCH_CHECK(rc == 0, "attention_bf16: unsupported shape S=", S, " D=", D);
   return out;
 }
@@ -612,16 +634,18 @@ torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 // qkv [B,S,3,H,D] (the QKV linear's output reshaped) → O [B,S,H*D];
 // the kernel reads strided rows directly — no permute/contiguous copies.
 torch::Tensor attention_qkv_bf16(torch::Tensor qkv, double scale,
-                                 int64_t pad) {
+                                 int64_t pad,
+                                 c10::optional<torch::Tensor> lens) {
   check_cuda(qkv, "qkv");
   TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv must be [B,S,3,H,D]");
   int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
+  const bool masked = check_lens(lens, B, qkv);
   auto out = torch::empty({B, S, H * D}, qkv.options());
-  int rc = launch_attention_qkv_bf16_pad(qkv.data_ptr(), out.data_ptr(),
-                                         (int)B, (int)H, (int)S, (int)D,
-                                         (float)scale, (int)pad,
-                                         cur_stream());
+  int rc = launch_attention_qkv_bf16_pad(
+      qkv.data_ptr(), out.data_ptr(), (int)B, (int)H, (int)S, (int)D,
+      (float)scale, (int)pad, masked ? lens->data_ptr<int32_t>() : nullptr,
+      cur_stream());
   TORCH_CHECK(rc == 0, "attention_qkv_bf16: unsupported shape S=", S,
               " D=", D);
   return out;
@@ -1141,7 +1165,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("take_binary", &take_binary);
   m.def("bytes_match", &bytes_match);
   m.def("attention_qkv_bf16", &attention_qkv_bf16, py::arg("qkv"),
-        py::arg("scale"), py::arg("pad") = 8);
+        py::arg("scale"), py::arg("pad") = 8, py::arg("lens") = py::none());
   m.def("mask_to_indices", &mask_to_indices);
   m.def("filter_cmp_scalar", &filter_cmp_scalar);
   m.def("gather", &gather);
@@ -1158,7 +1182,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_act_bf16", &bias_act_bf16, py::arg("x"),
         py::arg("bias") = py::none(), py::arg("act") = 0);
   m.def("attention_bf16", &attention_bf16, py::arg("q"), py::arg("k"),
-        py::arg("v"), py::arg("scale"));
+        py::arg("v"), py::arg("scale"), py::arg("lens") = py::none());
   m.def("proto_decode", &proto_decode, py::arg("data"),
         py::arg("offsets"), py::arg("fno"), py::arg("kind"),
         py::arg("is_float"), py::arg("slot"), py::arg("n_int"),

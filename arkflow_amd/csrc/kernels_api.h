@@ -19,17 +19,22 @@ void launch_bias_act_bf16(const void* x, const float* bias, void* out,
                           int64_t rows, int n, int act, hipStream_t st);
 
 // ---- attention.hip: each returns 0, or -1 for an unsupported (S, D) ---------
+// lens: nullptr (every key of every sequence is valid: the unmasked kernels),
+// or a device array of valid lengths that the kernels clamp to [0, S] and
+// the host never reads. It has one entry per kernel "batch" row: B for the
+// [B,S,3,H,D] layout (index bh / Hd), BH for packed [B,H,S,D] (Hd = 1).
 int launch_attention_bf16(const void* Q, const void* K, const void* V,
                           void* O, int BH, int S, int D, float scale,
-                          hipStream_t st);
+                          const int32_t* lens, hipStream_t st);
 int launch_attention_flash(const void* Q, const void* K, const void* V,
                            void* O, int BH, int S, int D, float scale,
-                           int ldq, int ldo, int Hd, hipStream_t st);
+                           int ldq, int ldo, int Hd, const int32_t* lens,
+                           hipStream_t st);
 int launch_attention_qkv_bf16(const void* QKV, void* O, int B, int H, int S,
                               int D, float scale, hipStream_t st);
 int launch_attention_qkv_bf16_pad(const void* QKV, void* O, int B, int H,
                                   int S, int D, float scale, int pad,
-                                  hipStream_t st);
+                                  const int32_t* lens, hipStream_t st);
 
 // ---- proto_decode.hip -------------------------------------------------------
 void launch_proto_copy_bytes(const uint8_t* data, const int64_t* start,

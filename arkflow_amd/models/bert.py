@@ -71,30 +71,45 @@ class BertEncoder:
         # whole forward (~80 kernel launches) replays as ONE graph launch
         import os as _os
         self.use_graph = _os.environ.get("ARKFLOW_BERT_GRAPH", "1") != "0"
-        self._graphs = {}  # (B, S) → (graph, static_ids, static_logits)
+        # (B, S) → (graph, static_ids, static_logits); masked forwards are
+        # keyed ("masked", B rounded up to 8, S) → (graph, static_ids,
+        # static_lens, static_logits)
+        self._graphs = {}
 
     # -------------------------------------------------------------- forward
-    def forward(self, token_ids: torch.Tensor) -> torch.Tensor:
-        """token_ids: [B, S] int64 → logits [B, num_labels] float32."""
+    def forward(self, token_ids: torch.Tensor,
+                lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """token_ids: [B, S] int64 → logits [B, num_labels] float32.
+
+        lengths: optional int [B] tensor; sequence b then consists of its
+        first lengths[b] tokens only, and logits row b depends on nothing
+        else in the batch (a length of 0 gives finite, meaningless logits)."""
         if self.use_graph and self.device.type == "cuda":
-            return self._forward_graphed(token_ids)
-        return self._forward_eager(token_ids)
+            if lengths is None:
+                return self._forward_graphed(token_ids)
+            return self._forward_graphed_masked(token_ids, lengths)
+        return self._forward_eager(token_ids, lengths)
+
+    def _capture(self, static_ids, static_lens=None):
+        """Warm up on a side stream (allocator settles), then capture one
+        eager forward over the static buffers. Returns (graph, logits)."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._forward_eager(static_ids, static_lens)
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            static_logits = self._forward_eager(static_ids, static_lens)
+        return graph, static_logits
 
     def _forward_graphed(self, token_ids: torch.Tensor) -> torch.Tensor:
         key = tuple(token_ids.shape)
         entry = self._graphs.get(key)
         if entry is None:
             static_ids = token_ids.to(self.device).clone()
-            # warmup on a side stream (allocator settles), then capture
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._forward_eager(static_ids)
-            torch.cuda.current_stream().wait_stream(s)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                static_logits = self._forward_eager(static_ids)
+            graph, static_logits = self._capture(static_ids)
             entry = (graph, static_ids, static_logits)
             self._graphs[key] = entry
         graph, static_ids, static_logits = entry
@@ -102,29 +117,62 @@ class BertEncoder:
         graph.replay()
         return static_logits
 
-    def _forward_eager(self, token_ids: torch.Tensor) -> torch.Tensor:
+    def _forward_graphed_masked(self, token_ids: torch.Tensor,
+                                lengths: torch.Tensor) -> torch.Tensor:
+        """One graph per (B rounded up to a multiple of 8, S): a stream whose
+        document count changes from batch to batch then replays a handful of
+        graphs and does not capture one per distinct B. The extra rows have
+        ids 0 and length 0; their logits are dropped."""
+        B, S = token_ids.shape
+        Bp = -(-B // 8) * 8
+        key = ("masked", Bp, S)
+        entry = self._graphs.get(key)
+        if entry is None:
+            static_ids = torch.zeros(Bp, S, dtype=torch.int64,
+                                     device=self.device)
+            static_lens = torch.zeros(Bp, dtype=torch.int32,
+                                      device=self.device)
+            graph, static_logits = self._capture(static_ids, static_lens)
+            entry = (graph, static_ids, static_lens, static_logits)
+            self._graphs[key] = entry
+        graph, static_ids, static_lens, static_logits = entry
+        static_ids[:B].copy_(token_ids.to(self.device))
+        static_ids[B:].zero_()
+        static_lens[:B].copy_(lengths.to(self.device))
+        static_lens[B:].zero_()
+        graph.replay()
+        return static_logits[:B].clone()
+
+    def _forward_eager(self, token_ids: torch.Tensor,
+                       lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         c = self.cfg
         B, S = token_ids.shape
         ids = token_ids.to(self.device)
+        lens = None if lengths is None else \
+            lengths.to(self.device, torch.int32).contiguous()
         x = self.tok_emb[ids.reshape(-1) % c.vocab_size].reshape(B, S, c.hidden)
         x = x + self.pos_emb[:S].unsqueeze(0)
         x = opsnn.layernorm_bf16(x.contiguous(), self.emb_gamma, self.emb_beta)
         for ly in self.layers:
-            x = self._layer(x, ly, B, S)
+            x = self._layer(x, ly, B, S, lens)
         cls = x[:, 0, :].contiguous()  # [B, hidden]
         pooled = opsnn.linear_bf16(cls, self.pool_w, self.pool_b, act="none")
         pooled = torch.tanh(pooled.float()).to(torch.bfloat16)
         logits = opsnn.linear_bf16(pooled, self.cls_w, self.cls_b)
         return logits.float()
 
-    def _layer(self, x: torch.Tensor, ly: dict, B: int, S: int) -> torch.Tensor:
+    def _layer(self, x: torch.Tensor, ly: dict, B: int, S: int,
+               lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         c = self.cfg
         h = c.hidden
         x2 = x.reshape(B * S, h)
         qkv = opsnn.linear_bf16(x2, ly["wqkv"], ly["bqkv"])  # [B*S, 3h]
         qkv = qkv.reshape(B, S, 3, c.heads, c.head_dim)
         # strided attention straight off the QKV tensor (no transposes)
-        attn = opsnn.attention_qkv_bf16(qkv, self._scale).reshape(B * S, h)
+        # (lens: rows ≥ lens[b] of sequence b are padding — masked as keys,
+        # written as 0 as queries)
+        attn = opsnn.attention_qkv_bf16(qkv, self._scale,
+                                        lens).reshape(B * S, h)
         proj = opsnn.linear_bf16(attn, ly["wo"], ly["bo"])
         x = opsnn.layernorm_bf16(proj.reshape(B, S, h), ly["ln1_g"],
                                  ly["ln1_b"], residual=x)

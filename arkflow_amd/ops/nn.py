@@ -101,42 +101,95 @@ def softmax_bf16(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     return torch.softmax(x.float() * scale, dim=-1).to(x.dtype)
 
 
+def _lens_i32(lengths: torch.Tensor, device: torch.device) -> torch.Tensor:
+    """Valid key counts as contiguous int32 on `device` (a no-op for a tensor
+    that already is). Values are not read on the host; every consumer treats
+    L < 0 as 0 and L > S as S."""
+    return lengths.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _masked_attention_f32(q, k, v, scale, lengths, softmax):
+    """The variable-length contract out of whole-tensor ops: keys >= L are
+    masked to -inf before the softmax, V rows >= L are replaced by 0 with a
+    select (a NaN there must not meet a zero probability in the product) and
+    output rows >= L are written as +0. `softmax(scores)` returns the
+    probabilities; rows with L == 0 come back NaN from it and are selected
+    away."""
+    S = q.shape[-2]
+    L = _lens_i32(lengths, q.device).view(-1, 1, 1, 1)
+    pos = torch.arange(S, device=q.device, dtype=torch.int32)
+    key_ok = pos.view(1, 1, 1, S) < L
+    row_ok = pos.view(1, 1, S, 1) < L
+    scores = torch.matmul(q, k.transpose(-1, -2))
+    scores = torch.where(key_ok, scores,
+                         torch.full_like(scores, float("-inf")))
+    p = softmax(scores)
+    p = torch.where(key_ok & row_ok, p, torch.zeros_like(p))
+    out = torch.matmul(p, torch.where(row_ok, v, torch.zeros_like(v)))
+    return torch.where(row_ok, out, torch.zeros_like(out))
+
+
 def attention_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                   scale: float) -> torch.Tensor:
+                   scale: float,
+                   lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused attention for [B,H,S,D] bf16. GPU: one-workgroup-per-(b,h)
     MFMA kernel (csrc/attention.hip) for its supported tile (S=128, D=64 —
     the BERT-base shape); other shapes compose batched hipBLASLt GEMMs with
-    our softmax kernel. CPU: fp32 reference."""
+    our softmax kernel. CPU: fp32 reference.
+
+    lengths: optional int [B] tensor of valid key counts, 0 <= L <= S. Row b
+    then attends over its first L keys only, its output rows >= L are +0, and
+    whatever q, k and v hold at rows >= L (NaN included) is ignored."""
     if q.is_cuda:
         nat = require_native()
         qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+        if lengths is not None:
+            lengths = _lens_i32(lengths, q.device)
         try:
-            return nat.attention_bf16(qc, kc, vc, scale)
+            if lengths is None:
+                return nat.attention_bf16(qc, kc, vc, scale)
+            return nat.attention_bf16(qc, kc, vc, scale, lens=lengths)
         except RuntimeError as e:
             if "unsupported shape" not in str(e):
                 raise
+        if lengths is not None:
+            return _masked_attention_f32(
+                qc, kc, vc, scale, lengths,
+                lambda sc: nat.softmax_bf16(
+                    sc.reshape(-1, sc.shape[-1]).contiguous(),
+                    scale).reshape(sc.shape))
         scores = torch.matmul(qc, kc.transpose(-1, -2))
         p = nat.softmax_bf16(scores.reshape(-1, scores.shape[-1]).contiguous(),
                              scale).reshape(scores.shape)
         return torch.matmul(p, vc)
+    if lengths is not None:
+        return _masked_attention_f32(
+            q.float(), k.float(), v.float(), scale, lengths,
+            lambda sc: torch.softmax(sc * scale, dim=-1)).to(q.dtype)
     p = torch.softmax(q.float() @ k.float().transpose(-1, -2) * scale, dim=-1)
     return (p @ v.float()).to(q.dtype)
 
 
-def attention_qkv_bf16(qkv: torch.Tensor, scale: float) -> torch.Tensor:
+def attention_qkv_bf16(qkv: torch.Tensor, scale: float,
+                       lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Attention straight from the QKV projection: qkv [B,S,3,H,D] bf16 →
     [B,S,H*D]. GPU: strided-load kernel, zero transpose copies; shapes the
-    kernel doesn't cover (or CPU) go through the permuted path."""
+    kernel doesn't cover (or CPU) go through the permuted path. `lengths`
+    as in attention_bf16."""
     B, S, three, H, D = qkv.shape
     if qkv.is_cuda:
         nat = require_native()
         try:
-            return nat.attention_qkv_bf16(qkv.contiguous(), scale)
+            if lengths is None:
+                return nat.attention_qkv_bf16(qkv.contiguous(), scale)
+            return nat.attention_qkv_bf16(
+                qkv.contiguous(), scale,
+                lens=_lens_i32(lengths, qkv.device))
         except RuntimeError as e:
             if "unsupported shape" not in str(e):
                 raise
     q = qkv[:, :, 0].permute(0, 2, 1, 3).contiguous()
     k = qkv[:, :, 1].permute(0, 2, 1, 3).contiguous()
     v = qkv[:, :, 2].permute(0, 2, 1, 3).contiguous()
-    attn = attention_bf16(q, k, v, scale)
+    attn = attention_bf16(q, k, v, scale, lengths)
     return attn.permute(0, 2, 1, 3).reshape(B, S, H * D)

@@ -43,6 +43,10 @@ class InferenceProcessor(Processor):
                 num_labels=int(config.get("num_labels", 2)),
             )
             self.token_column = config.get("token_column", "token")
+            # optional: a numeric column whose runs of equal consecutive
+            # values delimit variable-length sequences (a document id per
+            # token row); unset = fixed seq_len chunks of the token column
+            self.sequence_column = config.get("sequence_column")
             self.model = BertEncoder(cfg, self.device, self.seed)
             self.seq_len = cfg.seq_len
         else:
@@ -80,9 +84,38 @@ class InferenceProcessor(Processor):
                                                               scores)})
 
     # -------------------------------------------------------------- bert path
+    def _pack_sequences(self, tokens: torch.Tensor, seq_key: torch.Tensor):
+        """Runs of equal consecutive `seq_key` values → (ids [n_seq, seq_len]
+        zero-padded, lengths [n_seq] int32, the run's key [n_seq]). A run
+        longer than seq_len keeps its first seq_len tokens. Device ops only,
+        but for the one host read of the run count that sizes `ids`."""
+        keys, counts = torch.unique_consecutive(seq_key, return_counts=True)
+        starts = torch.cumsum(counts, 0) - counts
+        run = torch.repeat_interleave(
+            torch.arange(keys.shape[0], device=tokens.device), counts)
+        pos = torch.arange(tokens.shape[0], device=tokens.device) - starts[run]
+        keep = pos < self.seq_len
+        ids = torch.zeros(keys.shape[0], self.seq_len, dtype=torch.int64,
+                          device=tokens.device)
+        ids.index_put_((run[keep], pos[keep]), tokens[keep])
+        lengths = counts.clamp(max=self.seq_len).to(torch.int32)
+        return ids, lengths, keys
+
     def _process_bert(self, batch: MessageBatch) -> MessageBatch:
         tokens = batch.column(self.token_column).data.to(
             self.device, torch.int64)
+        if self.sequence_column:
+            seq_key = batch.column(self.sequence_column).data.to(self.device)
+            ids, lengths, keys = self._pack_sequences(tokens, seq_key)
+            logits = self.model.forward(ids, lengths)  # [n_seq, num_labels]
+            cols = {self.sequence_column: Column("numeric", keys)}
+            cols.update({
+                f"logit_{i}": Column("numeric", logits[:, i].contiguous())
+                for i in range(logits.shape[1])
+            })
+            cols[self.output_column] = Column(
+                "numeric", torch.argmax(logits, dim=1).to(torch.int64))
+            return MessageBatch(cols, input_name=batch.input_name)
         n_seq = tokens.shape[0] // self.seq_len
         if n_seq == 0:
             # short batch: pad one sequence with zeros
@@ -103,7 +136,12 @@ class InferenceProcessor(Processor):
 
 @register("processor", "inference",
           description="Native ML inference (mlp_anomaly per-row score; "
-                      "bert_base per-sequence logits) — bf16 MFMA kernels",
+                      "bert_base per-sequence logits) — bf16 MFMA kernels. "
+                      "bert_base: set sequence_column (e.g. a document id "
+                      "per token row) for variable-length sequences — one "
+                      "output row per run of equal ids, padding masked out "
+                      "of attention; unset = fixed seq_len chunks of "
+                      "token_column",
           example={"type": "inference", "model": "mlp_anomaly",
                    "columns": ["f0", "f1"], "output_column": "score"})
 def _build_inference(config: dict, resource=None) -> InferenceProcessor:
