@@ -588,19 +588,30 @@ torch::Tensor bias_act_bf16(torch::Tensor x,
   return out;
 }
 
-// Valid-length argument of the attention bindings: absent, or an int32 [B]
-// contiguous device tensor. Checked before any launch; its VALUES are never
-// read on the host (no sync, capturable) — the kernels clamp them to [0, S].
-static bool check_lens(const c10::optional<torch::Tensor>& lens, int64_t B,
-                       const torch::Tensor& like) {
-  if (!lens.has_value() || !lens->defined()) return false;
+// Valid-length argument of the attention bindings: absent (an undefined
+// tensor is returned: the unmasked kernels), or an int32 [B] contiguous
+// device tensor. Checked before any launch; its VALUES are never read on the
+// host (no sync, capturable) — the kernels clamp them to [0, S].
+static torch::Tensor check_lens(const c10::optional<torch::Tensor>& lens,
+                                int64_t B, const torch::Tensor& like) {
+  if (!lens.has_value() || !lens->defined()) return {};
   TORCH_CHECK(lens->is_cuda() && lens->device() == like.device(),
               "lens must be on the inputs' device");
   TORCH_CHECK(lens->scalar_type() == torch::kInt32, "lens must be int32");
   TORCH_CHECK(lens->dim() == 1 && lens->size(0) == B,
               "lens must be 1-D of length B=", B);
   TORCH_CHECK(lens->is_contiguous(), "lens must be contiguous");
-  return true;
+  return *lens;
+}
+
+// What both attention bindings do once their layout is in `a`: `lens` is
+// check_lens' result with a.B entries.
+static void run_attention(const char* name, AttnArgs a,
+                          const torch::Tensor& lens) {
+  a.lens = lens.defined() ? lens.data_ptr<int32_t>() : nullptr;
+  a.stream = cur_stream();
+  int rc = launch_attention_bf16(&a);
+  TORCH_CHECK(rc == 0, name, ": unsupported shape S=", a.S, " D=", a.D);
 }
 
 torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -618,16 +629,15 @@ torch::Tensor attention_bf16(torch::Tensor q, torch::Tensor k, torch::Tensor v,
               "k and v must match q's shape");
   int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   // the packed layout is BH independent rows: one length per (b, h)
-  torch::Tensor lens_bh;
-  if (check_lens(lens, B, q))
-    lens_bh = H == 1 ? *lens : lens->repeat_interleave(H).contiguous();
+  torch::Tensor lens_bh = check_lens(lens, B, q);
+  if (lens_bh.defined() && H != 1)
+    lens_bh = lens_bh.repeat_interleave(H).contiguous();
   auto out = torch::empty_like(q);
-  int rc = launch_attention_bf16(
-      q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)(B * H),
-      (int)S, (int)D, (float)scale,
-      lens_bh.defined() ? lens_bh.data_ptr<int32_t>() : nullptr,
-      cur_stream());
-  TORCH_CHECK(rc == 0, "attention_bf16: unsupported shape S=", S, " D=", D);
+  run_attention("attention_bf16",
+                {q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                 (int)(B * H), 1, (int)S, (int)D, (int)D, (int)D, (float)scale,
+                 8},
+                lens_bh);
   return out;
 }
 
@@ -640,14 +650,14 @@ torch::Tensor attention_qkv_bf16(torch::Tensor qkv, double scale,
   TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16, "qkv must be bf16");
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "qkv must be [B,S,3,H,D]");
   int64_t B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
-  const bool masked = check_lens(lens, B, qkv);
+  torch::Tensor lens_b = check_lens(lens, B, qkv);
   auto out = torch::empty({B, S, H * D}, qkv.options());
-  int rc = launch_attention_qkv_bf16_pad(
-      qkv.data_ptr(), out.data_ptr(), (int)B, (int)H, (int)S, (int)D,
-      (float)scale, (int)pad, masked ? lens->data_ptr<int32_t>() : nullptr,
-      cur_stream());
-  TORCH_CHECK(rc == 0, "attention_qkv_bf16: unsupported shape S=", S,
-              " D=", D);
+  const at::BFloat16* base = qkv.data_ptr<at::BFloat16>();
+  run_attention("attention_qkv_bf16",
+                {base, base + H * D, base + 2 * H * D, out.data_ptr(), (int)B,
+                 (int)H, (int)S, (int)D, (int)(3 * H * D), (int)(H * D),
+                 (float)scale, (int)pad},
+                lens_b);
   return out;
 }
 

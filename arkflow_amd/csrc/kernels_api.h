@@ -18,23 +18,32 @@ void launch_softmax_bf16(const void* x, void* out, int64_t rows, int n,
 void launch_bias_act_bf16(const void* x, const float* bias, void* out,
                           int64_t rows, int n, int act, hipStream_t st);
 
-// ---- attention.hip: each returns 0, or -1 for an unsupported (S, D) ---------
-// lens: nullptr (every key of every sequence is valid: the unmasked kernels),
-// or a device array of valid lengths that the kernels clamp to [0, S] and
-// the host never reads. It has one entry per kernel "batch" row: B for the
-// [B,S,3,H,D] layout (index bh / Hd), BH for packed [B,H,S,D] (Hd = 1).
-int launch_attention_bf16(const void* Q, const void* K, const void* V,
-                          void* O, int BH, int S, int D, float scale,
-                          const int32_t* lens, hipStream_t st);
-int launch_attention_flash(const void* Q, const void* K, const void* V,
-                           void* O, int BH, int S, int D, float scale,
-                           int ldq, int ldo, int Hd, const int32_t* lens,
-                           hipStream_t st);
-int launch_attention_qkv_bf16(const void* QKV, void* O, int B, int H, int S,
-                              int D, float scale, hipStream_t st);
-int launch_attention_qkv_bf16_pad(const void* QKV, void* O, int B, int H,
-                                  int S, int D, float scale, int pad,
-                                  const int32_t* lens, hipStream_t st);
+// ---- attention.hip ----------------------------------------------------------
+// Fused attention over B·Hd (batch, head) pairs. Row s of head h in batch b
+// is at base + ((int64_t)b*S + s)*ld + h*D, ld = ldq for q/k/v, ldo for o:
+//   packed [B,H,S,D]:  B = B·H, Hd = 1, ldq = ldo = D (one head per "batch"
+//                      row, so one length per (b, h));
+//   [B,S,3,H,D] → [B,S,H·D]:  Hd = H, q/k/v = base + {0,1,2}·H·D,
+//                      ldq = 3·H·D, ldo = H·D (no transpose copies).
+struct AttnArgs {
+  const void *q, *k, *v;  // bf16
+  void* o;                // bf16
+  int B;                  // batch rows = entries of lens
+  int Hd;                 // heads per batch row
+  int S, D;
+  int ldq, ldo;
+  float scale;
+  int pad;  // LDS row padding of the S=128 kernel in bf16 elements: 4, 8
+            // (production), 16 or 20; anything else runs as 8
+  // nullptr (every key of every sequence is valid: the unmasked kernels), or
+  // a device array of B valid lengths that the kernels clamp to [0, S] and
+  // the host never reads (capturable)
+  const int32_t* lens;
+  hipStream_t stream;
+};
+// S=128, D=64: the full-S kernel; else D=64, S%64==0: the flash-tiled
+// kernel; else nothing is launched and -1 is returned. 0 otherwise.
+int launch_attention_bf16(const AttnArgs* args);
 
 // ---- proto_decode.hip -------------------------------------------------------
 void launch_proto_copy_bytes(const uint8_t* data, const int64_t* start,

@@ -108,19 +108,21 @@ def _lens_i32(lengths: torch.Tensor, device: torch.device) -> torch.Tensor:
     return lengths.to(device=device, dtype=torch.int32).contiguous()
 
 
-def _masked_attention_f32(q, k, v, scale, lengths, softmax):
-    """The variable-length contract out of whole-tensor ops: keys >= L are
-    masked to -inf before the softmax, V rows >= L are replaced by 0 with a
-    select (a NaN there must not meet a zero probability in the product) and
-    output rows >= L are written as +0. `softmax(scores)` returns the
-    probabilities; rows with L == 0 come back NaN from it and are selected
-    away."""
+def _unfused_attention(q, k, v, lengths, softmax):
+    """Attention out of whole-tensor ops; `softmax(scores)` returns the
+    probabilities of the unscaled scores. With `lengths`, the variable-length
+    contract: keys >= L are masked to -inf before the softmax, V rows >= L
+    are replaced by 0 with a select (a NaN there must not meet a zero
+    probability in the product) and output rows >= L are written as +0; rows
+    with L == 0 come back NaN from the softmax and are selected away."""
+    scores = torch.matmul(q, k.transpose(-1, -2))
+    if lengths is None:
+        return torch.matmul(softmax(scores), v)
     S = q.shape[-2]
     L = _lens_i32(lengths, q.device).view(-1, 1, 1, 1)
     pos = torch.arange(S, device=q.device, dtype=torch.int32)
     key_ok = pos.view(1, 1, 1, S) < L
     row_ok = pos.view(1, 1, S, 1) < L
-    scores = torch.matmul(q, k.transpose(-1, -2))
     scores = torch.where(key_ok, scores,
                          torch.full_like(scores, float("-inf")))
     p = softmax(scores)
@@ -146,28 +148,18 @@ def attention_bf16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         if lengths is not None:
             lengths = _lens_i32(lengths, q.device)
         try:
-            if lengths is None:
-                return nat.attention_bf16(qc, kc, vc, scale)
             return nat.attention_bf16(qc, kc, vc, scale, lens=lengths)
         except RuntimeError as e:
             if "unsupported shape" not in str(e):
                 raise
-        if lengths is not None:
-            return _masked_attention_f32(
-                qc, kc, vc, scale, lengths,
-                lambda sc: nat.softmax_bf16(
-                    sc.reshape(-1, sc.shape[-1]).contiguous(),
-                    scale).reshape(sc.shape))
-        scores = torch.matmul(qc, kc.transpose(-1, -2))
-        p = nat.softmax_bf16(scores.reshape(-1, scores.shape[-1]).contiguous(),
-                             scale).reshape(scores.shape)
-        return torch.matmul(p, vc)
-    if lengths is not None:
-        return _masked_attention_f32(
-            q.float(), k.float(), v.float(), scale, lengths,
-            lambda sc: torch.softmax(sc * scale, dim=-1)).to(q.dtype)
-    p = torch.softmax(q.float() @ k.float().transpose(-1, -2) * scale, dim=-1)
-    return (p @ v.float()).to(q.dtype)
+        return _unfused_attention(
+            qc, kc, vc, lengths,
+            lambda sc: nat.softmax_bf16(
+                sc.reshape(-1, sc.shape[-1]).contiguous(),
+                scale).reshape(sc.shape))
+    return _unfused_attention(
+        q.float(), k.float(), v.float(), lengths,
+        lambda sc: torch.softmax(sc * scale, dim=-1)).to(q.dtype)
 
 
 def attention_qkv_bf16(qkv: torch.Tensor, scale: float,
@@ -180,11 +172,10 @@ def attention_qkv_bf16(qkv: torch.Tensor, scale: float,
     if qkv.is_cuda:
         nat = require_native()
         try:
-            if lengths is None:
-                return nat.attention_qkv_bf16(qkv.contiguous(), scale)
             return nat.attention_qkv_bf16(
                 qkv.contiguous(), scale,
-                lens=_lens_i32(lengths, qkv.device))
+                lens=None if lengths is None
+                else _lens_i32(lengths, qkv.device))
         except RuntimeError as e:
             if "unsupported shape" not in str(e):
                 raise

@@ -27,10 +27,12 @@ F64 = R.F64
 # (B, H, S, D), lens. S=128: the full-S kernel at its 16-column fragment,
 # 32-column K-step and 32-row wave edges. S=192/320: the flash kernel at its
 # 64-column KV-tile and 128-row Q-block edges, partial last Q block included.
+# S=64: the flash kernel's smallest shape, one KV tile, waves 2 and 3 past S.
 VARLEN_CASES = (
     ((10, 2, 128, 64), (1, 15, 16, 17, 32, 33, 64, 96, 127, 128)),
     ((8, 2, 192, 64), (1, 63, 64, 65, 128, 129, 191, 192)),
     ((10, 1, 320, 64), (1, 64, 127, 128, 129, 200, 256, 257, 319, 320)),
+    ((6, 2, 64, 64), (1, 31, 32, 33, 63, 64)),
 )
 VARLEN_FAMILIES = ("randn", "scale1", "lastkey", "poison")
 POISON = (float("nan"), float("inf"), -float("inf"), 3e38)
