@@ -5,7 +5,9 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <limits>
 #include <tuple>
 #include <vector>
 
@@ -1167,6 +1169,138 @@ proto_decode(
   return {out_i, out_f, err, strings, summary};
 }
 
+// ---------------------------------------------------------------------- window
+// Segmented inclusive scan of double[n] under uint8 head flags
+// (csrc/window.hip): tile aggregates → one-block carry scan → write.
+torch::Tensor seg_scan(const torch::Tensor& vals, const torch::Tensor& head,
+                       int op, bool reverse) {
+  int64_t n = vals.numel();
+  auto out = torch::empty_like(vals);
+  if (n == 0) return out;
+  int nt = seg_scan_tiles(n);
+  auto tile_v = torch::empty({nt}, vals.options());
+  auto carry = torch::empty({nt}, vals.options());
+  auto tile_f = torch::empty({nt}, head.options());
+  launch_segmented_scan(vals.data_ptr<double>(), head.data_ptr<uint8_t>(), n,
+                        op, reverse, tile_v.data_ptr<double>(),
+                        tile_f.data_ptr<uint8_t>(), carry.data_ptr<double>(),
+                        out.data_ptr<double>(), cur_stream());
+  return out;
+}
+
+void check_rows(const torch::Tensor& t, const char* name,
+                torch::ScalarType ty, int64_t n) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
+  TORCH_CHECK(t.dim() == 1 && t.numel() == n, name, " must have one entry ",
+              "per row");
+}
+
+torch::Tensor segmented_scan(torch::Tensor vals, torch::Tensor head,
+                             int64_t op, bool reverse) {
+  int64_t n = vals.numel();
+  TORCH_CHECK(n < (int64_t(1) << 31), "row indices are int32");
+  TORCH_CHECK(op >= SCAN_SUM && op <= SCAN_MAX, "unknown scan op ", op);
+  check_rows(vals, "values", torch::kFloat64, n);
+  check_rows(head, "head", torch::kUInt8, n);
+  return seg_scan(vals, head, (int)op, reverse);
+}
+
+// One window function over ROWS frames. Inputs are in sorted (partition,
+// order key) row order; row i's frame is rows [i+lo, i+hi] of its partition
+// (lo / hi absent: unbounded). Returns (result f64[n], valid u8[n]) scattered
+// through perm when given. Nothing here reads device memory on the host.
+std::tuple<torch::Tensor, torch::Tensor> window_frame(
+    torch::Tensor vals, c10::optional<torch::Tensor> valid,
+    torch::Tensor part, c10::optional<int64_t> lo, c10::optional<int64_t> hi,
+    int64_t func, c10::optional<torch::Tensor> perm) {
+  int64_t n = part.numel();
+  TORCH_CHECK(n < (int64_t(1) << 31), "row indices are int32");
+  TORCH_CHECK(func >= WF_SUM && func <= WF_COUNT_STAR,
+              "unknown window function ", func);
+  TORCH_CHECK(!lo || !hi || *lo <= *hi, "frame start is after frame end");
+  check_rows(part, "partition ids", torch::kInt64, n);
+  check_rows(vals, "values", torch::kFloat64, n);
+  if (valid) check_rows(*valid, "validity", torch::kUInt8, n);
+  if (perm) check_rows(*perm, "perm", torch::kInt64, n);
+  auto f64 = vals.options();
+  auto u8 = vals.options().dtype(torch::kUInt8);
+  auto out = torch::empty({n}, f64);
+  auto out_valid = torch::empty({n}, u8);
+  if (n == 0) return {out, out_valid};
+  auto st = cur_stream();
+  // an offset of n rows already leaves every partition: clamping keeps
+  // i + lo and hi - lo + 1 far from overflow without changing any frame
+  if (lo) lo = std::max(-n, std::min(n, *lo));
+  if (hi) hi = std::max(-n, std::min(n, *hi));
+
+  // partition bounds per row
+  auto head = torch::empty({n}, u8), tail = torch::empty({n}, u8);
+  auto head_idx = torch::empty({n}, f64), tail_idx = torch::empty({n}, f64);
+  launch_win_bounds(part.data_ptr<int64_t>(), n, head.data_ptr<uint8_t>(),
+                    tail.data_ptr<uint8_t>(), head_idx.data_ptr<double>(),
+                    tail_idx.data_ptr<double>(), st);
+  auto start = seg_scan(head_idx, head, SCAN_MAX, false);
+  auto end = seg_scan(tail_idx, tail, SCAN_MIN, true);
+
+  const bool is_sum = func == WF_SUM || func == WF_AVG;
+  const bool is_minmax = func == WF_MIN || func == WF_MAX;
+  const bool sliding = is_minmax && lo && hi;
+  const bool need_count = valid && (is_sum || is_minmax || func == WF_COUNT);
+  const int64_t width = sliding ? *hi - *lo + 1 : 1;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double fill = func == WF_MIN ? inf : func == WF_MAX ? -inf : 0.0;
+
+  torch::Tensor masked, ones, chunk_head, chunk_tail, prefix, suffix, count;
+  if (is_sum || is_minmax) masked = torch::empty({n}, f64);
+  if (need_count) ones = torch::empty({n}, f64);
+  if (sliding) {
+    chunk_head = torch::empty({n}, u8);
+    chunk_tail = torch::empty({n}, u8);
+  }
+  auto ptr_f64 = [](const torch::Tensor& t) {
+    return t.defined() ? t.data_ptr<double>() : nullptr;
+  };
+  auto ptr_u8 = [](const torch::Tensor& t) {
+    return t.defined() ? t.data_ptr<uint8_t>() : nullptr;
+  };
+  const uint8_t* valid_p = valid ? valid->data_ptr<uint8_t>() : nullptr;
+  if (masked.defined() || ones.defined())
+    launch_win_inputs(vals.data_ptr<double>(), valid_p,
+                      start.data_ptr<double>(), end.data_ptr<double>(), n,
+                      fill, width, ptr_f64(masked), ptr_f64(ones),
+                      ptr_u8(chunk_head), ptr_u8(chunk_tail), st);
+  if (need_count) count = seg_scan(ones, head, SCAN_SUM, false);
+  if (is_sum) prefix = seg_scan(masked, head, SCAN_SUM, false);
+  if (is_minmax) {
+    const int op = func == WF_MIN ? SCAN_MIN : SCAN_MAX;
+    if (sliding || !lo)
+      prefix = seg_scan(masked, sliding ? chunk_head : head, op, false);
+    if (sliding || lo)
+      suffix = seg_scan(masked, sliding ? chunk_tail : tail, op, true);
+  }
+
+  FrameArgs a{};
+  a.start = start.data_ptr<double>();
+  a.end = end.data_ptr<double>();
+  a.vals = vals.data_ptr<double>();
+  a.valid = valid_p;
+  a.prefix = ptr_f64(prefix);
+  a.suffix = ptr_f64(suffix);
+  a.count = ptr_f64(count);
+  a.perm = perm ? perm->data_ptr<int64_t>() : nullptr;
+  a.lo = lo.value_or(0);
+  a.hi = hi.value_or(0);
+  a.lo_unbounded = !lo;
+  a.hi_unbounded = !hi;
+  a.func = (int)func;
+  a.n = n;
+  a.out = out.data_ptr<double>();
+  a.out_valid = out_valid.data_ptr<uint8_t>();
+  launch_win_frame(&a, st);
+  return {out, out_valid};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1217,4 +1351,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gen_fields", &gen_fields);
   m.def("featpack", &featpack);
   m.def("radix_argsort", &radix_argsort, py::arg("keys"), py::arg("descending") = false);
+  m.def("segmented_scan", &segmented_scan, py::arg("values"), py::arg("head"),
+        py::arg("op"), py::arg("reverse") = false);
+  m.def("seg_scan_tile_rows", &seg_scan_tile_rows);
+  m.def("window_frame", &window_frame, py::arg("values"), py::arg("valid"),
+        py::arg("part"), py::arg("lo"), py::arg("hi"), py::arg("func"),
+        py::arg("perm") = py::none());
 }

@@ -1,7 +1,7 @@
 // Host-side interface of the relational kernels (WHERE, gather, GROUP BY,
-// join, ORDER BY and the scans between their passes). Included by the .hip
-// file that defines each launcher and by bindings.cpp, so a declaration that
-// drifts from its definition is a compile error.
+// join, ORDER BY, window frames and the scans between their passes). Included
+// by the .hip file that defines each launcher and by bindings.cpp, so a
+// declaration that drifts from its definition is a compile error.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,7 +17,52 @@ struct Predicate {
   double scalar;
 };
 
+// Segmented-scan operator and window function of a framed evaluation.
+enum ScanOpKind { SCAN_SUM = 0, SCAN_MIN = 1, SCAN_MAX = 2 };
+enum WindowFunc {
+  WF_SUM = 0, WF_COUNT = 1, WF_AVG = 2, WF_MIN = 3, WF_MAX = 4,
+  WF_FIRST = 5, WF_LAST = 6, WF_COUNT_STAR = 7
+};
+// Inputs of the frame kernel, all in sorted (partition, order) row order.
+// Row i's frame is [max(start, i+lo), min(end, i+hi)] clipped to its
+// partition; an unbounded side ignores lo / hi.
+struct FrameArgs {
+  const double* start;    // first row of the row's partition
+  const double* end;      // last row of the row's partition
+  const double* vals;     // raw values (first/last_value), else unused
+  const uint8_t* valid;   // null: no NULL input
+  const double* prefix;   // forward scan: sums, or min/max
+  const double* suffix;   // backward min/max scan
+  const double* count;    // forward scan of valid rows; null: no NULL input
+  const int64_t* perm;    // null: results stay in sorted order
+  int64_t lo, hi;
+  int lo_unbounded, hi_unbounded;
+  int func;               // WindowFunc
+  int64_t n;
+  double* out;            // out[perm[i]]
+  uint8_t* out_valid;     // 0 = NULL result
+};
+
 extern "C" {
+
+// ---- window.hip: segmented scan, window frames ------------------------------
+int seg_scan_tiles(int64_t n);  // entries of tile_v / tile_f / carry
+int seg_scan_tile_rows();
+// Inclusive scan of vals restarting at every row whose head flag is set; in
+// reverse the scan runs from row n-1 down. op is a ScanOpKind.
+void launch_segmented_scan(const double* vals, const uint8_t* head, int64_t n,
+                           int op, int reverse, double* tile_v,
+                           uint8_t* tile_f, double* carry, double* out,
+                           hipStream_t st);
+void launch_win_bounds(const int64_t* part, int64_t n, uint8_t* head,
+                       uint8_t* tail, double* head_idx, double* tail_idx,
+                       hipStream_t st);
+void launch_win_inputs(const double* vals, const uint8_t* valid,
+                       const double* start, const double* end, int64_t n,
+                       double fill, int64_t width, double* masked,
+                       double* ones, uint8_t* chunk_head, uint8_t* chunk_tail,
+                       hipStream_t st);
+void launch_win_frame(const FrameArgs* args, hipStream_t st);
 
 // ---- filter.hip: compaction, gather -----------------------------------------
 int filter_grid(int64_t n);  // blocks (= entries of counts / offs) for n rows

@@ -150,6 +150,166 @@ def sort_indices(key: torch.Tensor, ascending: bool = True) -> torch.Tensor:
     return torch.argsort(key, stable=True, descending=not ascending)
 
 
+# --------------------------------------------------------------------- window
+_SCAN_OPS = {"sum": 0, "min": 1, "max": 2}
+_SCAN_IDENTITY = {"sum": 0.0, "min": float("inf"), "max": float("-inf")}
+_WINDOW_FUNCS = {"sum": 0, "count": 1, "avg": 2, "min": 3, "max": 4,
+                 "first_value": 5, "last_value": 6, "count_star": 7}
+
+
+def segmented_scan(values: torch.Tensor, head: torch.Tensor, op: str,
+                   reverse: bool = False) -> torch.Tensor:
+    """Inclusive scan (op in sum|min|max) that restarts at every row whose
+    head flag is set; float64 in and out. With ``reverse`` the scan runs from
+    the last row down and a flag marks the first row met in that direction.
+
+    GPU: three-pass tile scan carrying (value, seen-a-head) pairs
+    (csrc/window.hip). CPU: log-step doubling over whole tensors, one step
+    per power of two up to the longest segment.
+    """
+    if op not in _SCAN_OPS:
+        raise ValueError(f"unknown scan op {op!r}")
+    v = values.to(torch.float64).contiguous()
+    h = head.to(torch.uint8).contiguous()
+    if v.shape != h.shape or v.dim() != 1:
+        raise ValueError("values and head must be 1-D and equally long")
+    if _use_native(v):
+        return require_native().segmented_scan(v, h, _SCAN_OPS[op], reverse)
+    if reverse:
+        return _segmented_scan_torch(v.flip(0), h.flip(0), op).flip(0)
+    return _segmented_scan_torch(v, h, op)
+
+
+def _segmented_scan_torch(v: torch.Tensor, head: torch.Tensor, op: str
+                          ) -> torch.Tensor:
+    n = v.shape[0]
+    y = v.clone()
+    seen = head.bool().clone()
+    if n:
+        seen[0] = True  # nothing precedes row 0
+    fn = {"sum": torch.add, "min": torch.minimum, "max": torch.maximum}[op]
+    shift = 1
+    # after the step with `shift`, y[i] covers the 2*shift rows ending at i
+    # (or back to the nearest head); done once every row has seen a head
+    while shift < n and not bool(seen.all()):
+        open_ = ~seen[shift:]
+        y[shift:] = torch.where(open_, fn(y[:-shift], y[shift:]), y[shift:])
+        seen[shift:] |= seen[:-shift].clone()
+        shift <<= 1
+    return y
+
+
+def window_frame(values: Optional[torch.Tensor],
+                 valid: Optional[torch.Tensor], part_ids: torch.Tensor,
+                 lo: Optional[int], hi: Optional[int], func: str,
+                 perm: Optional[torch.Tensor] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One window function over ``ROWS BETWEEN lo AND hi`` frames.
+
+    Rows arrive sorted by (partition, order key): ``values`` (None for
+    count_star) and ``valid`` (None = no NULL input) are per row, ``part_ids``
+    are the sorted partition ids. ``lo``/``hi`` are signed row offsets from
+    the current row, None = unbounded. func: sum|count|avg|min|max|
+    first_value|last_value|count_star. Returns (float64 result, bool valid);
+    both go to row ``perm[i]`` when ``perm`` is given, else stay sorted.
+
+    GPU: segmented scans + one frame kernel (csrc/window.hip). CPU: the same
+    scheme in torch — prefix differences for sum/count/avg, two scans over
+    chunks of the frame width for a sliding min/max.
+    """
+    if func not in _WINDOW_FUNCS:
+        raise ValueError(f"unknown window function {func!r}")
+    if lo is not None and hi is not None and lo > hi:
+        raise ValueError("frame start is after frame end")
+    n = part_ids.shape[0]
+    device = part_ids.device
+    if values is None:
+        values = torch.zeros(n, dtype=torch.float64, device=device)
+    v = values.to(torch.float64).contiguous()
+    if _use_native(part_ids):
+        out, ok = require_native().window_frame(
+            v, None if valid is None else valid.to(torch.uint8).contiguous(),
+            part_ids.to(torch.int64).contiguous(), lo, hi,
+            _WINDOW_FUNCS[func],
+            None if perm is None else perm.to(torch.int64).contiguous())
+        return out, ok.bool()
+    out, ok = _window_frame_torch(v, valid, part_ids, lo, hi, func)
+    if perm is not None:
+        p = perm.long()
+        out = torch.empty_like(out).index_copy_(0, p, out)
+        ok = torch.empty_like(ok).index_copy_(0, p, ok)
+    return out, ok
+
+
+def _window_frame_torch(v, valid, part, lo, hi, func):
+    n = part.shape[0]
+    device = part.device
+    if n == 0:
+        return (torch.empty(0, dtype=torch.float64, device=device),
+                torch.empty(0, dtype=torch.bool, device=device))
+    ar = torch.arange(n, dtype=torch.int64, device=device)
+    head = torch.ones(n, dtype=torch.bool, device=device)
+    head[1:] = part[1:] != part[:-1]
+    tail = torch.ones(n, dtype=torch.bool, device=device)
+    tail[:-1] = head[1:]
+    inf = float("inf")
+    start = segmented_scan(torch.where(head, ar, 0).double(), head,
+                           "max").long()
+    end = segmented_scan(torch.where(tail, ar.double(), inf), tail, "min",
+                         reverse=True).long()
+    # an offset of n rows already leaves every partition
+    l = start if lo is None else torch.maximum(start, ar + max(-n, min(n, lo)))
+    r = end if hi is None else torch.minimum(end, ar + max(-n, min(n, hi)))
+    empty = l > r
+    lc, rc = l.clamp(0, n - 1), r.clamp(0, n - 1)  # gather-safe when empty
+    at_start = l == start
+    before = (l - 1).clamp(0, n - 1)
+
+    def prefix_diff(p):
+        return p[rc] - torch.where(at_start, torch.zeros_like(p), p[before])
+
+    rows = (r - l + 1).clamp(min=0).double()
+    if valid is None:
+        cnt = rows
+    else:
+        cnt = torch.where(empty, torch.zeros_like(rows), prefix_diff(
+            segmented_scan(valid.double(), head, "sum")))
+    some = cnt > 0
+    if func == "count_star":
+        return rows, torch.ones_like(empty)
+    if func == "count":
+        return cnt, torch.ones_like(empty)
+    if func in ("first_value", "last_value"):
+        at = lc if func == "first_value" else rc
+        ok = ~empty if valid is None else ~empty & valid.bool()[at]
+        return torch.where(ok, v[at], torch.zeros_like(v)), ok
+    fill = _SCAN_IDENTITY["sum" if func in ("sum", "avg") else func]
+    masked = v if valid is None else torch.where(
+        valid.bool(), v, torch.full_like(v, fill))
+    if func in ("sum", "avg"):
+        res = prefix_diff(segmented_scan(masked, head, "sum"))
+        if func == "avg":
+            res = res / cnt.clamp(min=1)
+    elif lo is None:
+        res = segmented_scan(masked, head, func)[rc]
+    elif hi is None:
+        res = segmented_scan(masked, tail, func, reverse=True)[lc]
+    else:
+        # sliding min/max (van Herk/Gil-Werman): chunks of w rows from the
+        # partition start; a frame spans at most two of them
+        w = max(-n, min(n, hi)) - max(-n, min(n, lo)) + 1
+        pos = (ar - start) % w
+        prefix = segmented_scan(masked, pos == 0, func)
+        suffix = segmented_scan(masked, (pos == w - 1) | tail, func,
+                                reverse=True)
+        fn = torch.minimum if func == "min" else torch.maximum
+        same = (lc - start) // w == (rc - start) // w
+        res = torch.where(
+            same, torch.where((lc - start) % w == 0, prefix[rc], suffix[lc]),
+            fn(suffix[lc], prefix[rc]))
+    return torch.where(some, res, torch.zeros_like(res)), some
+
+
 # ----------------------------------------------------------------------- join
 def join_inner(left_keys: torch.Tensor, right_keys: torch.Tensor
                ) -> Tuple[torch.Tensor, torch.Tensor]:

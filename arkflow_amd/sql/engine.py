@@ -38,6 +38,10 @@ from .parser import (
 
 DEFAULT_TABLE = "flow"  # reference processor/sql.rs registers the batch as `flow`
 
+# window functions whose result depends on the frame clause
+_FRAMED_FUNCS = ("sum", "count", "avg", "min", "max", "first_value",
+                 "last_value")
+
 
 class SqlExecutor:
     """Pre-parsed, reusable statement (reference pre-parses once, sql.rs:189)."""
@@ -510,6 +514,52 @@ class SqlExecutor:
         out[perm] = out_sorted
         return out
 
+    def _framed_window(self, w_: FuncCall, gid: torch.Tensor, env: Env):
+        """ROWS BETWEEN lo AND hi: sort by (partition, ORDER BY keys) — the
+        stable sort keeps input order where there are no keys — and evaluate
+        every row's frame with ops.window_frame (csrc/window.hip on GPU)."""
+        device = env.device
+        n = env.n_rows
+        name = w_.name
+        _, lo, hi = w_.over.frame
+        star = name == "count" and (not w_.args
+                                    or isinstance(w_.args[0], Star))
+        vals = valid = None
+        if not star:
+            if not w_.args or isinstance(w_.args[0], Star):
+                raise SqlError(f"{name}() requires a value argument")
+            v0 = eval_expr(w_.args[0], env)
+            if isinstance(v0, Column) and v0.kind != "numeric":
+                raise SqlError(f"{name}() over a ROWS frame needs a numeric "
+                               "argument")
+            vals = v0.data if isinstance(v0, Column) else as_tensor(v0, env)
+            from .eval import expr_validity
+            valid = expr_validity(w_.args[0], env)
+            if isinstance(v0, Column) and v0.validity is not None:
+                valid = v0.validity if valid is None else valid & v0.validity
+        perm = torch.arange(n, dtype=torch.int64, device=device)
+        for e, asc in reversed(w_.over.order_by):
+            v = eval_expr(e, env)
+            key = v.data if isinstance(v, Column) and v.kind == "numeric" \
+                else as_tensor(v, env)
+            perm = perm[ops.sort_indices(key[perm], ascending=asc)]
+        perm = perm[ops.sort_indices(gid[perm], ascending=True)]
+        out, ok = ops.window_frame(
+            None if star else vals[perm].double(),
+            None if valid is None else valid[perm], gid[perm], lo, hi,
+            "count_star" if star else name, perm)
+        if name == "count":
+            return out.long()
+        if name in ("first_value", "last_value"):
+            out = out.to(vals.dtype)
+        # NULL results: an empty frame (one that cannot hold its own row) or
+        # a frame with no valid input. The validity must be attached whenever
+        # the input has one, or the projection would apply the input's.
+        if valid is not None or (lo is not None and lo > 0) \
+                or (hi is not None and hi < 0):
+            return Column("numeric", out, validity=ok)
+        return out
+
     def _compute_window(self, w_: FuncCall, env: Env) -> torch.Tensor:
         """Window functions over PARTITION BY (full-partition frame):
         row_number/rank/dense_rank and partition-wide aggregates."""
@@ -530,13 +580,25 @@ class SqlExecutor:
             gid = torch.zeros(n, dtype=torch.int64, device=device)
             g = 1
         name = w_.name
+        # frame clause: ROWS frames have their own path; of RANGE only the two
+        # forms the code below already computes parse (running and whole
+        # partition). The rank family, lag/lead and window UDFs ignore it.
+        frame = w_.over.frame
+        whole = frame is not None and frame[1] is None and frame[2] is None
+        if frame is not None and name in _FRAMED_FUNCS and (
+                frame[0] == "rows" or (whole and name == "last_value")):
+            # last_value over the whole partition: RANGE and ROWS agree
+            return self._framed_window(w_, gid, env)
+        if name == "last_value":
+            raise SqlError("last_value() needs a ROWS frame or RANGE BETWEEN "
+                           "UNBOUNDED PRECEDING AND UNBOUNDED FOLLOWING")
         if name in ("sum", "count", "avg", "min", "max"):
             if name == "count" and (not w_.args or isinstance(w_.args[0],
                                                               Star)):
                 vals = torch.ones(n, device=device)
             else:
                 vals = as_tensor(eval_expr(w_.args[0], env), env)
-            if w_.over.order_by:
+            if w_.over.order_by and not whole:
                 # running aggregate: the standard's default frame with
                 # ORDER BY is RANGE UNBOUNDED PRECEDING..CURRENT ROW —
                 # equal peers share the frame end (sqlite/DataFusion)

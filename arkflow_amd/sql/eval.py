@@ -59,6 +59,14 @@ class Env:
                        f"{ref.name}; have {sorted(self.columns)}")
 
 
+def _frame_bound_name(off: Optional[int], is_start: bool) -> str:
+    if off is None:
+        return "unbounded preceding" if is_start else "unbounded following"
+    if off == 0:
+        return "current row"
+    return f"{-off} preceding" if off < 0 else f"{off} following"
+
+
 def expr_name(e) -> str:
     """Readable output-column name for an unaliased projection."""
     if isinstance(e, ColumnRef):
@@ -74,7 +82,14 @@ def expr_name(e) -> str:
             part = ", ".join(expr_name(p) for p in e.over.partition_by)
             ob = ", ".join(expr_name(o) + ("" if asc else " desc")
                            for o, asc in e.over.order_by)
-            base += f" over(partition by {part} order by {ob})"
+            frame = ""
+            if e.over.frame is not None:
+                # part of the key under which window results are stored: two
+                # calls that differ only in frame are two results
+                unit, lo, hi = e.over.frame
+                frame = (f" {unit} between {_frame_bound_name(lo, True)}"
+                         f" and {_frame_bound_name(hi, False)}")
+            base += f" over(partition by {part} order by {ob}{frame})"
         return base
     if isinstance(e, Star):
         return "*"

@@ -56,6 +56,9 @@ class UnaryOp:
 class WindowSpec:
     partition_by: list
     order_by: list  # [(expr, asc)]
+    # (unit, lo, hi): unit "rows" | "range"; lo / hi are signed row offsets
+    # from the current row (k PRECEDING = -k), None = unbounded
+    frame: Optional[tuple] = None
 
 
 @dataclass
@@ -278,6 +281,82 @@ class Parser:
             raise SqlError(
                 f"expected {value or kind}, got {got.value!r} at {got.pos}")
         return t
+
+    # window frame clause. Its words (rows, range, unbounded, preceding,
+    # following, current, row) are contextual: matched by spelling at this one
+    # position and ordinary identifiers everywhere else.
+    def _accept_word(self, *words: str) -> Optional[str]:
+        t = self.peek()
+        if t.kind in ("ident", "kw") and t.value.lower() in words:
+            self.next()
+            return t.value.lower()
+        return None
+
+    def _expect_word(self, word: str) -> None:
+        if self._accept_word(word) is None:
+            got = self.peek()
+            raise SqlError(f"expected {word.upper()} in window frame, got "
+                           f"{got.value!r} at {got.pos}")
+
+    def _frame_bound(self) -> Tuple[str, Optional[int]]:
+        """One frame bound → ("unbounded preceding" | "unbounded following" |
+        "offset" | "current row", signed row offset or None)."""
+        if self._accept_word("unbounded"):
+            side = self._accept_word("preceding", "following")
+            if side is None:
+                raise SqlError("expected PRECEDING or FOLLOWING after "
+                               f"UNBOUNDED at {self.peek().pos}")
+            return f"unbounded {side}", None
+        if self._accept_word("current"):
+            self._expect_word("row")
+            return "current row", 0
+        t = self.peek()
+        if t.kind != "number" or not t.value.isdigit():
+            raise SqlError("window frame offset must be a non-negative "
+                           f"integer literal, got {t.value!r} at {t.pos}")
+        self.next()
+        side = self._accept_word("preceding", "following")
+        if side is None:
+            raise SqlError("expected PRECEDING or FOLLOWING after frame "
+                           f"offset at {self.peek().pos}")
+        k = int(t.value)
+        return "offset", -k if side == "preceding" else k
+
+    def _parse_frame(self) -> Optional[tuple]:
+        """{ROWS | RANGE} {<bound> | BETWEEN <bound> AND <bound>} at the end
+        of an OVER (...) clause → (unit, lo, hi), or None when absent."""
+        t = self.peek()
+        if t.kind != "ident":
+            return None
+        unit = t.value.lower()
+        if unit == "groups":
+            raise SqlError("GROUPS window frames are not supported")
+        if unit not in ("rows", "range"):
+            return None
+        self.next()
+        if self.accept("kw", "between"):
+            lo_kind, lo = self._frame_bound()
+            self.expect("kw", "and")
+            hi_kind, hi = self._frame_bound()
+        else:
+            lo_kind, lo = self._frame_bound()
+            hi_kind, hi = "current row", 0
+        if self._accept_word("exclude"):
+            raise SqlError("window frame EXCLUDE is not supported")
+        if lo_kind == "unbounded following":
+            raise SqlError("window frame cannot start at UNBOUNDED FOLLOWING")
+        if hi_kind == "unbounded preceding":
+            raise SqlError("window frame cannot end at UNBOUNDED PRECEDING")
+        if lo is not None and hi is not None and lo > hi:
+            raise SqlError("window frame start is after its end")
+        if unit == "range":
+            if "offset" in (lo_kind, hi_kind):
+                raise SqlError("RANGE frames with a numeric offset are not "
+                               "supported; use ROWS")
+            if lo_kind == "current row":
+                raise SqlError("RANGE frames starting at CURRENT ROW are not "
+                               "supported; use ROWS")
+        return unit, lo, hi
 
     # entry
     def parse(self) -> Select:
@@ -613,8 +692,9 @@ class Parser:
                             order.append((e, asc))
                             if not self.accept("op", ","):
                                 break
+                    frame = self._parse_frame()
                     self.expect("op", ")")
-                    over = WindowSpec(part, order)
+                    over = WindowSpec(part, order, frame)
                 return FuncCall(name.lower(), args, distinct, over, filt)
             # qualified column
             if self.accept("op", "."):
