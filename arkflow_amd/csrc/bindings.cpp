@@ -195,7 +195,7 @@ std::tuple<torch::Tensor, torch::Tensor> hash_group_i64(torch::Tensor keys) {
     return {torch::empty({0}, opts32), torch::empty({0}, keys.options())};
   uint32_t tsize = next_pow2((uint32_t)std::max<int64_t>(n * 2, 64));
   auto table_keys = torch::empty({(int64_t)tsize}, keys.options());
-  auto table_gids = torch::empty({(int64_t)tsize}, opts32);
+  auto table_gids = torch::empty({(int64_t)tsize + 1}, opts32);
   auto counter = torch::zeros({1}, opts32);
   auto gids = torch::empty({n}, opts32);
   auto st = cur_stream();
@@ -247,7 +247,7 @@ std::tuple<torch::Tensor, torch::Tensor> join_inner_i64(torch::Tensor lk,
     return {torch::empty({0}, opts64), torch::empty({0}, opts64)};
   uint32_t tsize = next_pow2((uint32_t)std::max<int64_t>(nr * 2, 64));
   auto table_keys = torch::empty({(int64_t)tsize}, opts64);
-  auto table_head = torch::empty({(int64_t)tsize}, opts32);
+  auto table_head = torch::empty({(int64_t)tsize + 1}, opts32);
   auto next = torch::empty({nr}, opts32);
   auto st = cur_stream();
   launch_join_build(rk.data_ptr<int64_t>(), nr, table_keys.data_ptr<int64_t>(),
@@ -866,7 +866,7 @@ hash_agg_capture(torch::Tensor keys, torch::Tensor nrow,
   auto opts32 = keys.options().dtype(torch::kInt32);
   auto optsf = keys.options().dtype(torch::kFloat32);
   auto table_keys = torch::empty({table_size}, keys.options());
-  auto table_gids = torch::empty({table_size}, opts32);
+  auto table_gids = torch::empty({table_size + 1}, opts32);
   auto counter = torch::empty({1}, opts32);
   auto gids = torch::empty({std::max<int64_t>(n_cap, 1)}, opts32);
   auto counts = torch::empty({g_cap}, optsf);

@@ -32,9 +32,14 @@ DEV_INLINE float wave_reduce_max(float v) {
 
 // atomic float max/min via monotone flip to UNSIGNED int order
 // (the flipped values must be compared unsigned — top-bit-set patterns)
-DEV_INLINE uint32_t float_flip(float f) {
-  uint32_t u = (uint32_t)__float_as_int(f);
+DEV_INLINE uint32_t float_flip_bits(uint32_t u) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+DEV_INLINE uint32_t float_flip(float f) {
+  return float_flip_bits((uint32_t)__float_as_int(f));
+}
+DEV_INLINE bool f32_bits_nan(uint32_t u) {
+  return (u & 0x7fffffffu) > 0x7f800000u;
 }
 DEV_INLINE float float_unflip(uint32_t u) {
   return __int_as_float(
@@ -43,7 +48,11 @@ DEV_INLINE float float_unflip(uint32_t u) {
 
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Free-slot marker of the open-addressing tables (GROUP BY and join).
+// Free-slot marker of the open-addressing tables (GROUP BY and join). It is
+// INT64_MIN, which is also a legal key, so a row with that key never probes:
+// it owns the one extra slot at index table_size, which `& table_mask` cannot
+// reach. The per-slot int32 arrays (group ids, chain heads) are therefore
+// table_size + 1 long; the key array stays at table_size.
 #define EMPTY_KEY 0x8000000000000000ll
 
 // Where a kernel's row count comes from. The sync form of an operator knows

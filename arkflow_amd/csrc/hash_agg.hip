@@ -32,6 +32,12 @@ static int32_t float_flip_host(float f) {
 // Two kernels: INSERT claims keys and assigns dense gids; LOOKUP probes with
 // plain loads after the kernel boundary (which orders all insert writes) —
 // no per-row acquire/invalidate in the hot path.
+// table_gids has table_size + 1 entries. The last one belongs to the key
+// that equals EMPTY_KEY (common.h): such a row claims it through the gid word
+// (-1 free, -2 claimed, then the gid), still one atomic claim per new key.
+#define GID_FREE (-1)
+#define GID_CLAIMED (-2)
+
 template <typename Count>
 __global__ void hash_insert_kernel(const int64_t* __restrict__ keys,
                                    Count count,
@@ -44,6 +50,17 @@ __global__ void hash_insert_kernel(const int64_t* __restrict__ keys,
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     int64_t k = keys[i];
+    if (k == EMPTY_KEY) {
+      int32_t* slot = &table_gids[table_mask + 1];
+      if (__hip_atomic_load(slot, __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT) == GID_FREE &&
+          atomicCAS(slot, GID_FREE, GID_CLAIMED) == GID_FREE) {
+        int32_t gid = atomicAdd(counter, 1);
+        __hip_atomic_store(slot, gid, __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+      continue;
+    }
     uint32_t h = (uint32_t)(mix64((uint64_t)k) & table_mask);
     for (;;) {
       int64_t cur = __hip_atomic_load(&table_keys[h], __ATOMIC_RELAXED,
@@ -79,12 +96,15 @@ __global__ void hash_lookup_kernel(const int64_t* __restrict__ keys,
   for (; i < n; i += stride) {
     int64_t k = keys[i];
     uint32_t h = (uint32_t)(mix64((uint64_t)k) & table_mask);
-    while (table_keys[h] != k) h = (h + 1) & table_mask;
+    if (k == EMPTY_KEY)
+      h = table_mask + 1;
+    else
+      while (table_keys[h] != k) h = (h + 1) & table_mask;
     gids_out[i] = table_gids[h];
   }
 }
 
-// uniq[gid] = key
+// uniq[gid] = key, over the table_size probed slots and the reserved one
 template <bool Guard>
 __global__ void hash_export_kernel(const int64_t* __restrict__ table_keys,
                                    const int32_t* __restrict__ table_gids,
@@ -92,10 +112,11 @@ __global__ void hash_export_kernel(const int64_t* __restrict__ table_keys,
                                    int64_t* __restrict__ uniq) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t stride = gridDim.x * blockDim.x;
-  for (; i < table_size; i += stride) {
-    int64_t k = table_keys[i];
-    if (k == EMPTY_KEY) continue;
+  for (; i <= table_size; i += stride) {
+    bool reserved = i == table_size;
+    int64_t k = reserved ? EMPTY_KEY : table_keys[i];
     int32_t g = table_gids[i];
+    if (reserved ? g < 0 : k == EMPTY_KEY) continue;
     if (!Guard || (g >= 0 && g < g_cap)) uniq[g] = k;
   }
 }
@@ -132,6 +153,15 @@ __global__ void segment_sum_global_kernel(const float* __restrict__ vals,
 }
 
 // MIN/MAX on monotone-flipped int32 (handles negative floats correctly).
+// A NaN of either sign maps to the value that wins the reduction (0 for MIN,
+// all ones for MAX; both unflip to a NaN), so it propagates into its group
+// the way torch's amin / amax do.
+DEV_INLINE uint32_t mm_flip(float f, int op) {
+  uint32_t u = (uint32_t)__float_as_int(f);
+  if (f32_bits_nan(u)) return op == MIN ? 0u : 0xFFFFFFFFu;
+  return float_flip_bits(u);
+}
+
 __global__ void segment_mm_lds_kernel(const float* __restrict__ vals,
                                       const int32_t* __restrict__ gids,
                                       int64_t n, int g, int op,
@@ -143,7 +173,7 @@ __global__ void segment_mm_lds_kernel(const float* __restrict__ vals,
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    uint32_t v = float_flip(vals[i]);
+    uint32_t v = mm_flip(vals[i], op);
     if (op == MIN) atomicMin((uint32_t*)&part[gids[i]], v);
     else atomicMax((uint32_t*)&part[gids[i]], v);
   }
@@ -165,7 +195,7 @@ __global__ void segment_mm_global_kernel(const float* __restrict__ vals,
   for (; i < n; i += stride) {
     int g = gids[i];
     if (Guard && (unsigned)g >= (unsigned)g_cap) continue;
-    uint32_t v = float_flip(vals[i]);
+    uint32_t v = mm_flip(vals[i], op);
     if (op == MIN) atomicMin((uint32_t*)&out_flipped[g], v);
     else atomicMax((uint32_t*)&out_flipped[g], v);
   }
@@ -224,9 +254,9 @@ __global__ void agg_reset_kernel(int64_t* __restrict__ tk,
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   if (i == 0) *counter = 0;
-  for (int64_t j = i; j < ts; j += stride) {
-    tk[j] = EMPTY_KEY;
-    tg[j] = -1;
+  for (int64_t j = i; j <= ts; j += stride) {  // tg: ts + 1 entries
+    if (j < ts) tk[j] = EMPTY_KEY;
+    tg[j] = GID_FREE;
   }
   for (int64_t j = i; j < g_cap; j += stride) {
     counts[j] = 0.f;
@@ -261,7 +291,7 @@ void launch_hash_build(const int64_t* keys, int64_t n, int64_t* table_keys,
   fill_kernel<int64_t><<<capped_grid(table_size), 256, 0, st>>>(
       table_keys, EMPTY_KEY, table_size);
   fill_kernel<int32_t><<<capped_grid(table_size), 256, 0, st>>>(
-      table_gids, -1, table_size);
+      table_gids, GID_FREE, (int64_t)table_size + 1);
   int grid = capped_grid(n, AGG_BLOCK);
   hash_insert_kernel<<<grid, AGG_BLOCK, 0, st>>>(
       keys, HostCount{n}, table_keys, table_gids, table_size - 1, counter);
@@ -271,7 +301,8 @@ void launch_hash_build(const int64_t* keys, int64_t n, int64_t* table_keys,
 
 void launch_hash_export(const int64_t* table_keys, const int32_t* table_gids,
                         uint32_t table_size, int64_t* uniq, hipStream_t st) {
-  hash_export_kernel<false><<<capped_grid(table_size), 256, 0, st>>>(
+  hash_export_kernel<false><<<capped_grid((int64_t)table_size + 1), 256, 0,
+                              st>>>(
       table_keys, table_gids, table_size, 0, uniq);
 }
 
@@ -326,7 +357,9 @@ void launch_hash_agg_capture(const int64_t* keys, const int32_t* nrow,
       mi[i] = float_flip_host(ops[i] == MIN ? INFINITY : -INFINITY);
     }
   }
-  agg_reset_kernel<<<capped_grid(table_size > g_cap ? table_size : g_cap),
+  int64_t reset_n = (int64_t)table_size + 1;
+  if (reset_n < g_cap) reset_n = g_cap;
+  agg_reset_kernel<<<capped_grid(reset_n),
                      256, 0, st>>>(table_keys, table_gids, table_size,
                                    counter, counts, g_cap, sb[0], sb[1],
                                    sb[2], sb[3], mb[0], mb[1], mb[2], mb[3],
@@ -355,7 +388,8 @@ void launch_hash_agg_capture(const int64_t* keys, const int32_t* nrow,
                                                           red_out[i], g_cap);
     }
   }
-  hash_export_kernel<true><<<capped_grid(table_size), 256, 0, st>>>(
+  hash_export_kernel<true><<<capped_grid((int64_t)table_size + 1), 256, 0,
+                             st>>>(
       table_keys, table_gids, table_size, g_cap, uniq);
   if (counts_i64)
     counts_to_i64_kernel<<<capped_grid(g_cap), 256, 0, st>>>(counts, g_cap,

@@ -9,14 +9,21 @@
 
 extern "C" {
 
-// key transforms: float → monotone uint32; int → biased unsigned
+// key transforms: float → monotone uint32; int → biased unsigned.
+// Floats are canonicalised first so the order is torch's stable argsort:
+// -0.0 equals +0.0 (ties keep input order), and every NaN, whatever its sign
+// or payload, is one key that sorts last ascending; ~u puts it first
+// descending.
 __global__ void f32_to_ordered_u32(const float* __restrict__ in,
                                    uint32_t* __restrict__ out, int64_t n,
                                    int descending) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    uint32_t u = float_flip(in[i]);
+    uint32_t u = (uint32_t)__float_as_int(in[i]);
+    if (f32_bits_nan(u)) u = 0x7fffffffu;
+    else if (u == 0x80000000u) u = 0u;
+    u = float_flip_bits(u);
     out[i] = descending ? ~u : u;
   }
 }

@@ -94,6 +94,8 @@ void launch_scan_write(const int32_t* in, int64_t n, const int64_t* block_offs,
                        int64_t* out, hipStream_t st);
 
 // ---- hash_agg.hip -----------------------------------------------------------
+// table_size is a power of two. table_keys has table_size entries, table_gids
+// table_size + 1: the last belongs to the key equal to the free-slot marker.
 void launch_hash_build(const int64_t* keys, int64_t n, int64_t* table_keys,
                        int32_t* table_gids, uint32_t table_size,
                        int32_t* counter, int32_t* gids_out, hipStream_t st);
@@ -113,6 +115,7 @@ void launch_hash_agg_capture(const int64_t* keys, const int32_t* nrow,
                              int32_t* gcount_out, hipStream_t st);
 
 // ---- hash_join.hip ----------------------------------------------------------
+// Likewise table_head has table_size + 1 entries.
 void launch_join_build(const int64_t* rkeys, int64_t n_right,
                        int64_t* table_keys, int32_t* table_head, int32_t* next,
                        uint32_t table_size, hipStream_t st);

@@ -103,10 +103,12 @@ def segment_reduce(values: torch.Tensor, group_ids: torch.Tensor,
     """Per-group reduction: op in sum|min|max|count|mean."""
     gid = group_ids.long()
     if op == "count":
-        if values.is_cuda:
+        if values.is_cuda and values.shape[0] < (1 << 24):
             # int64 scatter_add on GPU is a CAS loop — catastrophic under
             # high key contention; the native f32 LDS-buffered sum is exact
             # for counts < 2^24 per group and orders of magnitude faster.
+            # No group can hold 2^24 rows when the batch has fewer; a larger
+            # batch counts in int64 below.
             ones = torch.ones(values.shape[0], dtype=torch.float32,
                               device=values.device)
             return segment_reduce(ones, group_ids, num_groups,
@@ -317,8 +319,15 @@ def join_inner(left_keys: torch.Tensor, right_keys: torch.Tensor
 
     GPU: build/probe hash-join kernel (csrc/hash_join.hip). CPU fallback:
     sort-merge via searchsorted (handles duplicate keys on both sides).
+    The kernel hashes int64 keys: floating-point keys are refused there
+    (TypeError) rather than truncated — encode them to integer ids first.
     """
     if _use_native(left_keys):
+        if left_keys.dtype.is_floating_point \
+                or right_keys.dtype.is_floating_point:
+            raise TypeError(
+                "join_inner on a device takes integer keys, got "
+                f"{left_keys.dtype} and {right_keys.dtype}")
         return require_native().join_inner_i64(
             left_keys.to(torch.int64), right_keys.to(torch.int64))
     return _join_sort_merge(left_keys, right_keys)

@@ -303,9 +303,10 @@ class SqlExecutor:
         # run after the set ops below)
         if sel.order_by and not self._setops:
             cur_cols = dict(env.columns)  # permuted alongside result
+            cur_aggs = dict(env.agg_results)  # likewise
             final_env = Env(
                 {**cur_cols, **result.columns},
-                result.num_rows, device, env.agg_results)
+                result.num_rows, device, cur_aggs)
             # multi-key sort: stable sorts applied last-key-first
             from .parser import Literal as _Lit
             out_names = list(result.columns)
@@ -352,9 +353,17 @@ class SqlExecutor:
                 # original env would drop earlier keys' permutations (bug
                 # caught by 3-key ORDER BY differential)
                 cur_cols = {k: c.take(idx) for k, c in cur_cols.items()}
+                # so are the aggregates an earlier key may name (ORDER BY
+                # sum(a) DESC, k): left in group order they only line up
+                # when the groups happen to come out sorted by the later
+                # keys, as torch.unique's do and the hash table's do not
+                cur_aggs = {
+                    k: (v.take(idx) if isinstance(v, Column) else v[idx])
+                    if len(v) == len(idx) else v
+                    for k, v in cur_aggs.items()}
                 final_env = Env(
                     {**cur_cols, **result.columns},
-                    result.num_rows, device, env.agg_results)
+                    result.num_rows, device, cur_aggs)
 
         # ---------------------------------------------------- offset / limit
         if not self._setops:
@@ -823,15 +832,14 @@ class SqlExecutor:
         for a, b in key_pairs:
             l_keys.append(as_tensor(eval_expr(a, l_env), l_env))
             r_keys.append(as_tensor(eval_expr(b, r_env), r_env))
-        lk, _, _ = (_encode_keys(l_keys, device) if len(l_keys) > 1
-                    else (l_keys[0], None, 0))
-        rk = r_keys[0] if len(r_keys) == 1 else None
-        if len(l_keys) > 1:
-            # co-encode both sides so hashes align
+        if len(l_keys) > 1 or l_keys[0].dtype.is_floating_point \
+                or r_keys[0].dtype.is_floating_point:
+            # several keys, or a floating-point one: co-encode both sides to
+            # shared integer ids. A cast to int64 would join 1.5 with 1.2.
             lk, rk = _co_encode(l_keys, r_keys, device)
-        lk = lk.to(torch.int64) if lk.dtype not in (
-            torch.int64, torch.float32) else lk
-        rk = rk.to(lk.dtype) if rk.dtype != lk.dtype else rk
+        else:
+            lk = l_keys[0].to(torch.int64)
+            rk = r_keys[0].to(torch.int64)
         # NULL join keys never match (SQL): drop invalid-key rows from each
         # side before the hash join, remapping indices back afterwards. For
         # LEFT joins, invalid-left rows re-enter unmatched (NULL right side).
@@ -1112,12 +1120,17 @@ def _split_and(e) -> list:
 
 
 def _to_column(v, env: Env) -> Column:
-    if isinstance(v, Column):
-        return v
     if isinstance(v, torch.Tensor):
         return Column("numeric", v)
     if isinstance(v, str):
-        return Column.from_strings([v] * env.n_rows)
+        v = Column.from_strings([v] * env.n_rows)
+    if isinstance(v, Column):
+        # string functions build their result on the host; a device batch
+        # keeps every column on the device, or a later take() by device
+        # indices (ORDER BY, DISTINCT) cannot gather it
+        if v.data.device.type != torch.device(env.device).type:
+            v = v.to(env.device)
+        return v
     # scalar broadcast
     return Column("numeric", as_tensor(v, env))
 
@@ -1160,8 +1173,13 @@ def _encode_keys(keys: list, device) -> Tuple[torch.Tensor, None, int]:
 
 
 def _co_encode(l_keys, r_keys, device):
+    """Group ids shared by both sides of a join: equal id <=> equal key
+    tuple. All-integer keys are compared as int64 (exact over the whole
+    range), anything else as float64 (exact for every f32 / f64 value)."""
     n_l = l_keys[0].shape[0]
-    combined = [torch.cat([l.to(torch.float64), r.to(torch.float64)])
+    all_int = all(not k.dtype.is_floating_point for k in l_keys + r_keys)
+    dt = torch.int64 if all_int else torch.float64
+    combined = [torch.cat([l.to(dt), r.to(dt)])
                 for l, r in zip(l_keys, r_keys)]
     gid, _, _ = _encode_keys(combined, device)
     return gid[:n_l], gid[n_l:]

@@ -6,6 +6,8 @@ Marked gpu; the driver runs them on a real MI355X.
 import pytest
 import torch
 
+from tests import relational_ref as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -65,14 +67,25 @@ def test_hash_group(nat, dev):
     assert int(gid.max()) == uniq.shape[0] - 1 and int(gid.min()) == 0
 
 
+def _assert_sum_within_bound(got, vals, gids, g):
+    """Segment sums against an fp64 host reference, group by group within
+    n_g * 2^-23 * sum|v| (tests/relational_ref.py sum_bound). With hundreds
+    of rows in a group that bound is wider than the 1e-2 + 1e-4 |ref| this
+    test asked for before, so the smaller of the two holds."""
+    s, _, _, rows, a = R.segment_ref(vals.cpu(), gids.cpu(), g)
+    bound = torch.minimum(R.sum_bound(rows, a), 1e-2 + 1e-4 * s.abs())
+    err = (got.cpu().double() - s).abs()
+    assert bool((err <= bound).all()), \
+        f"max excess {(err - bound).max().item():.3e}"
+
+
 def test_segment_reduce(nat, dev):
     torch.manual_seed(4)
     n, g = 500_000, 777
     gids = torch.randint(0, g, (n,), device=dev, dtype=torch.int32)
     vals = torch.randn(n, device=dev) * 10
-    exp_sum = torch.zeros(g, device=dev).scatter_add_(0, gids.long(), vals)
     got_sum = nat.segment_reduce_f32(vals, gids, g, 0)
-    assert torch.allclose(got_sum, exp_sum, atol=1e-2, rtol=1e-4)
+    _assert_sum_within_bound(got_sum, vals, gids, g)
     exp_min = torch.full((g,), float("inf"), device=dev).scatter_reduce_(
         0, gids.long(), vals, reduce="amin")
     got_min = nat.segment_reduce_f32(vals, gids, g, 1)
@@ -85,8 +98,7 @@ def test_segment_reduce(nat, dev):
     g2 = 50_000
     gids2 = torch.randint(0, g2, (n,), device=dev, dtype=torch.int32)
     got2 = nat.segment_reduce_f32(vals, gids2, g2, 0)
-    exp2 = torch.zeros(g2, device=dev).scatter_add_(0, gids2.long(), vals)
-    assert torch.allclose(got2, exp2, atol=1e-2, rtol=1e-4)
+    _assert_sum_within_bound(got2, vals, gids2, g2)
 
 
 def test_join_inner(nat, dev):
@@ -1427,9 +1439,8 @@ def test_segment_reduce_lds_global_boundary(nat, dev, g):
     n = 20_000
     gids = torch.randint(0, g, (n,), device=dev, dtype=torch.int32)
     vals = torch.randn(n, device=dev) * 10
-    exp_sum = torch.zeros(g, device=dev).scatter_add_(0, gids.long(), vals)
     got_sum = nat.segment_reduce_f32(vals, gids, g, 0)
-    assert torch.allclose(got_sum, exp_sum, atol=1e-2, rtol=1e-4)
+    _assert_sum_within_bound(got_sum, vals, gids, g)
     exp_min = torch.full((g,), float("inf"), device=dev).scatter_reduce_(
         0, gids.long(), vals, reduce="amin")
     assert torch.equal(nat.segment_reduce_f32(vals, gids, g, 1), exp_min)
