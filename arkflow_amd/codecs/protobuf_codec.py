@@ -7,8 +7,9 @@ from typing import List, Sequence
 import torch
 
 from ..batch import Column, MessageBatch
-from ..processors.proto_wire import decode_message, encode_message
-from ..processors.protobuf_proc import _load_schema
+from ..processors.proto_wire import decode_message
+from ..processors.protobuf_proc import (
+    _load_schema, encode_device, encode_rows_host, load_encoder_choice)
 from ..registry import register
 from ..spi import Codec
 
@@ -16,20 +17,19 @@ from ..spi import Codec
 class ProtobufCodec(Codec):
     def __init__(self, config: dict, resource=None):
         self.schema = _load_schema(config)
+        self.encoder = load_encoder_choice(config)
         self.device = getattr(resource, "device", None)
 
     def encode(self, batch: MessageBatch) -> List[bytes]:
-        rows = batch.to_rows()
-        out = []
-        for r in rows:
-            clean = {}
-            for name, (no, t) in self.schema.by_name.items():
-                v = r.get(name)
-                if isinstance(v, (bytes, bytearray)) and t == "string":
-                    v = v.decode("utf-8", "replace")
-                clean[name] = v
-            out.append(encode_message(clean, self.schema))
-        return out
+        """One message per row. A device-resident batch that the GPU encoder
+        takes (protobuf_proc.encode_device) is encoded there and comes back
+        in one device-to-host copy of data and offsets; anything else, or
+        ``encoder: host``, is encoded row by row on the host."""
+        if self.encoder == "auto" and batch.num_rows and \
+                encode_device(self.schema, batch.columns) is not None:
+            from .. import ops
+            return ops.proto_encode(batch, self.schema).to_pylist()
+        return encode_rows_host(batch, self.schema)
 
     def decode(self, payloads: Sequence[bytes]) -> MessageBatch:
         rows = [decode_message(p, self.schema) for p in payloads]
@@ -53,7 +53,8 @@ class ProtobufCodec(Codec):
 
 
 @register("codec", "protobuf",
-          description="batch ↔ scalar proto3 wire format",
+          description="batch ↔ scalar proto3 wire format (device-resident "
+                      "batches encode on the GPU, host batches on the host)",
           example={"type": "protobuf",
                    "proto": "message M { double v = 1; }"})
 def _build_protobuf_codec(config: dict, resource=None) -> ProtobufCodec:

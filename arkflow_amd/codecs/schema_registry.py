@@ -61,9 +61,18 @@ class SchemaRegistryCodec(Codec):
             {n: [r.get(n) for r in rows] for n in names})
 
     def encode(self, batch: MessageBatch) -> List[bytes]:
+        """Header + message per row. A device-resident batch that the GPU
+        encoder takes (protobuf_proc.encode_device) is encoded there, the
+        5-byte header going in as the kernel's row prefix, and comes back in
+        one device-to-host copy; anything else is encoded on the host."""
         from ..processors.proto_wire import encode_message
+        from ..processors.protobuf_proc import encode_device
         schema = self._resolve(self.default_id)
         header = bytes([MAGIC]) + struct.pack(">I", self.default_id)
+        if batch.num_rows and \
+                encode_device(schema, batch.columns) is not None:
+            from .. import ops
+            return ops.proto_encode(batch, schema, prefix=header).to_pylist()
         out = []
         for row in batch.to_rows():
             clean = {k: (v.decode("utf-8", "replace")
@@ -75,7 +84,8 @@ class SchemaRegistryCodec(Codec):
 
 @register("codec", "schema_registry",
           description="Confluent wire format [0x00][schema-id][payload] with "
-                      "per-id schema cache",
+                      "per-id schema cache (device-resident batches encode "
+                      "on the GPU, host batches on the host)",
           example={"type": "schema_registry",
                    "schemas": {"1": "message M { double v = 1; }"}})
 def _build_schema_registry(config, resource=None):

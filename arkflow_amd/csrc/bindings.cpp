@@ -1169,6 +1169,114 @@ proto_decode(
   return {out_i, out_f, err, strings, summary};
 }
 
+// Columns → one binary column of proto3 messages (csrc/proto_encode.hip):
+// size pass → offsets scan → ONE host readback [total_bytes, error] (the
+// total sizes the output) → write pass → wave-per-row payload copy.
+// Field f (ascending field number) reads row slot[f] of in_i64 / in_f64, or
+// string column slot[f]; valid_idx[f] indexes `valids` (uint8[n]) or is -1.
+// Returns (data, offsets, summary); on error (summary[1] != 0) data is empty.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> proto_encode(
+    torch::Tensor in_i64, torch::Tensor in_f64,
+    std::vector<std::tuple<torch::Tensor, torch::Tensor>> strings,
+    std::vector<int64_t> fno, std::vector<int64_t> kind,
+    std::vector<int64_t> slot, std::vector<torch::Tensor> valids,
+    std::vector<int64_t> valid_idx, std::string prefix) {
+  check_cuda(in_i64, "in_i64");
+  check_cuda(in_f64, "in_f64");
+  TORCH_CHECK(in_i64.scalar_type() == torch::kInt64 && in_i64.dim() == 2);
+  TORCH_CHECK(in_f64.scalar_type() == torch::kFloat64 && in_f64.dim() == 2);
+  const int64_t n = in_i64.size(1);
+  TORCH_CHECK(in_f64.size(1) == n, "in_f64 must have one column per row");
+  const size_t nf = fno.size();
+  TORCH_CHECK(nf <= PROTO_ENC_MAX_FIELDS, "too many fields for proto_encode");
+  TORCH_CHECK(kind.size() == nf && slot.size() == nf && valid_idx.size() == nf);
+  TORCH_CHECK(prefix.size() <= 8, "prefix is at most 8 bytes");
+  TORCH_CHECK(strings.size() <= PROTO_ENC_MAX_FIELDS);
+
+  ProtoEncSpec spec{};
+  spec.nf = (int)nf;
+  spec.ns = (int)strings.size();
+  spec.prefix_len = (int)prefix.size();
+  std::copy(prefix.begin(), prefix.end(), spec.prefix);
+  for (size_t s = 0; s < strings.size(); ++s) {
+    const auto& data = std::get<0>(strings[s]);
+    const auto& offs = std::get<1>(strings[s]);
+    check_cuda(data, "string data");
+    check_cuda(offs, "string offsets");
+    TORCH_CHECK(data.scalar_type() == torch::kUInt8);
+    TORCH_CHECK(offs.scalar_type() == torch::kInt64 && offs.numel() == n + 1,
+                "string offsets must be int64[n + 1]");
+    spec.sdata[s] = data.data_ptr<uint8_t>();
+    spec.soffs[s] = offs.data_ptr<int64_t>();
+    spec.sdata_len[s] = data.numel();
+  }
+  int64_t prev_fno = 0;
+  for (size_t f = 0; f < nf; ++f) {
+    TORCH_CHECK(fno[f] > prev_fno && fno[f] < (1ll << 29),
+                "field numbers must ascend within [1, 2^29)");
+    prev_fno = fno[f];
+    const int64_t k = kind[f];
+    int wire;
+    int64_t slots;
+    switch (k) {
+      case PROTO_ENC_VARINT: case PROTO_ENC_ZIGZAG:
+        wire = 0; slots = in_i64.size(0); break;
+      case PROTO_ENC_FIXED64: wire = 1; slots = in_i64.size(0); break;
+      case PROTO_ENC_FIXED32: case PROTO_ENC_SFIXED32:
+        wire = 5; slots = in_i64.size(0); break;
+      case PROTO_ENC_F64: wire = 1; slots = in_f64.size(0); break;
+      case PROTO_ENC_F32: wire = 5; slots = in_f64.size(0); break;
+      case PROTO_ENC_BYTES: wire = 2; slots = (int64_t)strings.size(); break;
+      default: TORCH_CHECK(false, "unknown proto_encode kind ", k);
+    }
+    TORCH_CHECK(slot[f] >= 0 && slot[f] < slots, "field slot out of range");
+    spec.tag[f] = (uint32_t)((fno[f] << 3) | wire);
+    spec.kind[f] = (uint8_t)k;
+    spec.slot[f] = (uint8_t)slot[f];
+    if (valid_idx[f] >= 0) {
+      TORCH_CHECK(valid_idx[f] < (int64_t)valids.size());
+      const auto& v = valids[valid_idx[f]];
+      check_cuda(v, "validity");
+      TORCH_CHECK(v.scalar_type() == torch::kUInt8 && v.dim() == 1 &&
+                      v.numel() == n,
+                  "validity must be uint8[n]");
+      spec.valid[f] = v.data_ptr<uint8_t>();
+    }
+  }
+
+  auto bytes_opt = in_i64.options().dtype(torch::kUInt8);
+  auto i64_opt = in_i64.options();
+  auto st = cur_stream();
+  if (n == 0)
+    return {torch::empty({0}, bytes_opt), torch::zeros({1}, i64_opt),
+            torch::zeros({2}, torch::kInt64)};
+  auto lens = torch::empty({n}, i64_opt.dtype(torch::kInt32));
+  auto err = torch::zeros({1}, i64_opt.dtype(torch::kInt32));
+  launch_proto_encode_size(&spec, in_i64.data_ptr<int64_t>(),
+                           in_f64.data_ptr<double>(), n,
+                           lens.data_ptr<int32_t>(), err.data_ptr<int32_t>(),
+                           st);
+  auto offs = exclusive_offsets(lens);
+  auto summary =
+      torch::cat({offs.narrow(0, n, 1), err.to(torch::kInt64)}).cpu();
+  const int64_t total = summary.data_ptr<int64_t>()[0];
+  if (summary.data_ptr<int64_t>()[1] != 0)
+    return {torch::empty({0}, bytes_opt), offs, summary};
+  auto out = torch::empty({std::max<int64_t>(total, 1)}, bytes_opt);
+  auto str_dst = torch::empty({std::max<int64_t>(spec.ns, 1), n}, i64_opt);
+  if (total > 0) {
+    launch_proto_encode_write(&spec, in_i64.data_ptr<int64_t>(),
+                              in_f64.data_ptr<double>(), n,
+                              offs.data_ptr<int64_t>(),
+                              out.data_ptr<uint8_t>(),
+                              str_dst.data_ptr<int64_t>(),
+                              err.data_ptr<int32_t>(), st);
+    launch_proto_encode_copy(&spec, n, str_dst.data_ptr<int64_t>(),
+                             out.data_ptr<uint8_t>(), total, st);
+  }
+  return {out.slice(0, 0, total), offs, summary};
+}
+
 // ---------------------------------------------------------------------- window
 // Segmented inclusive scan of double[n] under uint8 head flags
 // (csrc/window.hip): tile aggregates → one-block carry scan → write.
@@ -1331,6 +1439,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("offsets"), py::arg("fno"), py::arg("kind"),
         py::arg("is_float"), py::arg("slot"), py::arg("n_int"),
         py::arg("n_float"), py::arg("n_str"), py::arg("capture") = false);
+  m.def("proto_encode", &proto_encode, py::arg("in_i64"), py::arg("in_f64"),
+        py::arg("strings"), py::arg("fno"), py::arg("kind"), py::arg("slot"),
+        py::arg("valids"), py::arg("valid_idx"), py::arg("prefix") = "");
+  m.attr("PROTO_ENC_MAX_FIELDS") = PROTO_ENC_MAX_FIELDS;
   m.def("gather_columns", &gather_columns);
   m.def("gemm_bf16_variant", &gemm_bf16_variant);
   m.def("bytes_hash", &bytes_hash);

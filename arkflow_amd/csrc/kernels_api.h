@@ -56,6 +56,53 @@ void launch_proto_decode(const uint8_t* data, const int64_t* offsets,
                          int64_t* str_start, int32_t* str_len,
                          int32_t* err_flags, hipStream_t st);
 
+// ---- proto_encode.hip -------------------------------------------------------
+#define PROTO_ENC_MAX_FIELDS 32
+// wire forms of a field; values 0..7 match launch_proto_decode's kinds
+enum ProtoEncKind {
+  PROTO_ENC_VARINT = 0,    // int32/int64/uint32/uint64/bool
+  PROTO_ENC_ZIGZAG = 1,    // sint32/sint64
+  PROTO_ENC_F64 = 2,       // double
+  PROTO_ENC_F32 = 3,       // float: the float64 input rounded to float32
+  PROTO_ENC_FIXED64 = 4,   // fixed64/sfixed64: the int64's 8 bytes
+  PROTO_ENC_FIXED32 = 6,   // fixed32: error outside [0, 2^32)
+  PROTO_ENC_SFIXED32 = 7,  // sfixed32: error outside [-2^31, 2^31)
+  PROTO_ENC_BYTES = 9,     // string/bytes
+};
+// Fields in ascending field number; a schema field with no input column is
+// simply not listed. Passed to the kernels by value.
+struct ProtoEncSpec {
+  int nf;                                  // fields listed
+  int ns;                                  // string/bytes slots in use
+  int prefix_len;                          // <= 8
+  uint8_t prefix[8];                       // written at the start of each row
+  uint32_t tag[PROTO_ENC_MAX_FIELDS];      // (field number << 3) | wire type
+  uint8_t kind[PROTO_ENC_MAX_FIELDS];      // ProtoEncKind
+  // row of in_i64 (integer kinds) / in_f64 (F64, F32), or the string slot
+  uint8_t slot[PROTO_ENC_MAX_FIELDS];
+  const uint8_t* valid[PROTO_ENC_MAX_FIELDS];  // uint8[n], or null: no NULLs
+  // per string slot: the source column. Its offsets need not start at 0.
+  const uint8_t* sdata[PROTO_ENC_MAX_FIELDS];
+  const int64_t* soffs[PROTO_ENC_MAX_FIELDS];  // int64[n + 1]
+  int64_t sdata_len[PROTO_ENC_MAX_FIELDS];     // bytes behind sdata
+};
+// Size pass: lens[i] = encoded bytes of row i. err[0] is set to 1 for a
+// fixed32/sfixed32 value out of range, a finite value that overflows float32,
+// a source span outside its column, or a row longer than INT32_MAX.
+void launch_proto_encode_size(const ProtoEncSpec* spec, const int64_t* in_i64,
+                              const double* in_f64, int64_t n, int32_t* lens,
+                              int32_t* err, hipStream_t st);
+// Write pass: everything but the string/bytes payloads into out[out_offs[i]..
+// out_offs[i+1]); str_dst[s][i] = where the payload of slot s goes, or -1.
+void launch_proto_encode_write(const ProtoEncSpec* spec, const int64_t* in_i64,
+                               const double* in_f64, int64_t n,
+                               const int64_t* out_offs, uint8_t* out,
+                               int64_t* str_dst, int32_t* err, hipStream_t st);
+// Payload copy, one wave per row.
+void launch_proto_encode_copy(const ProtoEncSpec* spec, int64_t n,
+                              const int64_t* str_dst, uint8_t* out,
+                              int64_t out_len, hipStream_t st);
+
 // ---- json_decode.hip --------------------------------------------------------
 void launch_json_decode(const uint8_t* data, const int64_t* offsets,
                         int64_t n_docs, int nf, const char* names,

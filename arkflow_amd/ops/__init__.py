@@ -8,6 +8,7 @@ GPU test can never pass on a non-native path. On CPU, torch reference
 implementations keep CI green and serve as the numerics oracle.
 """
 from __future__ import annotations
+import struct
 from typing import Optional, Tuple
 
 import torch
@@ -310,6 +311,75 @@ def _window_frame_torch(v, valid, part, lo, hi, func):
             same, torch.where((lc - start) % w == 0, prefix[rc], suffix[lc]),
             fn(suffix[lc], prefix[rc]))
     return torch.where(some, res, torch.zeros_like(res)), some
+
+
+# ------------------------------------------------------------ protobuf encode
+def proto_encode(batch_or_columns, schema, prefix: bytes = b""):
+    """Encode each row as one scalar proto3 message of ``schema``: a
+    MessageBatch or a name → Column dict in, a binary Column on the inputs'
+    device out. ``prefix`` (at most 8 bytes, e.g. a schema-registry header)
+    opens every row. Columns are matched to fields by name; a field with no
+    column is absent, a NULL is absent, proto3 defaults are elided, and a
+    value its field cannot hold (fixed32/sfixed32 out of range, a finite
+    value beyond float32) raises ProcessError.
+
+    GPU: size pass + offsets scan + write pass + wave-per-row payload copy
+    (csrc/proto_encode.hip), one [total_bytes, error] readback. Integer fields
+    read their column cast to int64 (floats truncate toward zero), float
+    fields cast to float64; a ``string`` field's bytes are copied unchecked.
+    CPU, or an input the kernel does not take (see
+    protobuf_proc.encode_device): proto_wire.encode_message row by row, which
+    the GPU path matches byte for byte on valid UTF-8.
+    """
+    from ..batch import Column, MessageBatch
+    from ..errors import ProcessError
+    from ..processors.protobuf_proc import encode_device, encode_rows_host
+    prefix = bytes(prefix)
+    if len(prefix) > 8:
+        raise ValueError("proto_encode prefix is at most 8 bytes")
+    batch = batch_or_columns if isinstance(batch_or_columns, MessageBatch) \
+        else MessageBatch(dict(batch_or_columns))
+    plan = encode_device(schema, batch.columns)
+    if plan is None:
+        try:
+            rows = encode_rows_host(batch, schema)
+        except (OverflowError, ValueError, TypeError, struct.error) as e:
+            raise ProcessError(f"protobuf encode error: {e}") from e
+        return Column.from_bytes([prefix + r for r in rows]).to(batch.device)
+    spec, device = plan
+    n = batch.num_rows
+    cols = batch.columns
+
+    def widen(names, dtype):
+        rows = []
+        for name in names:
+            d = cols[name].data
+            if dtype is torch.float64 and d.dtype in (torch.bfloat16,
+                                                      torch.float16):
+                d = d.to(torch.float32)
+            rows.append(d.to(dtype))
+        if not rows:
+            return torch.empty((0, n), dtype=dtype, device=device)
+        return torch.stack(rows).contiguous()
+
+    valids, valid_idx = [], []
+    for name in spec.names:
+        v = cols[name].validity
+        valid_idx.append(-1 if v is None else len(valids))
+        if v is not None:
+            valids.append(v.to(torch.uint8).contiguous())
+    strings = [(cols[name].data.contiguous(), cols[name].offsets.contiguous())
+               for name in spec.str_fields]
+    data, offsets, summary = require_native().proto_encode(
+        widen(spec.int_fields, torch.int64),
+        widen(spec.float_fields, torch.float64), strings, spec.fno,
+        spec.kind, spec.slot, valids, valid_idx, prefix)
+    if int(summary[1]) != 0:
+        raise ProcessError(
+            "protobuf encode error: a value does not fit its field (fixed32 "
+            "/ sfixed32 out of range, float32 overflow) or a row exceeds "
+            "2 GiB")
+    return Column("binary", data, offsets)
 
 
 # ----------------------------------------------------------------------- join

@@ -5,11 +5,15 @@ component/protobuf.rs: dynamic decode/encode of scalar proto3 fields from a
 .proto source (no nested/repeated/map/oneof — header :14-25). The decode hot
 path is a GPU kernel parsing the device-resident binary column directly
 (csrc/proto_decode.hip) — numeric fields into typed columns, string/bytes
-fields via a two-pass span-record + copy-out into binary columns.
+fields via a two-pass span-record + copy-out into binary columns. The encode
+hot path is its inverse (csrc/proto_encode.hip, through ops.proto_encode): a
+size pass, an offsets scan, a write pass and a wave-per-row payload copy turn
+device-resident columns into a device-resident ``__value__`` column, byte for
+byte what the host codec (proto_wire.encode_message) writes row by row.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -67,6 +71,95 @@ def build_gpu_spec(schema):
             slot.append(len(int_fields))
             int_fields.append(name)
     return fno, kind, isf, slot, int_fields, float_fields, str_fields
+
+
+PROTO_ENC_MAX_FIELDS = 32  # csrc/kernels_api.h
+ENC_BYTES = 9
+_ENC_KIND = {
+    "int32": 0, "int64": 0, "uint32": 0, "uint64": 0, "bool": 0,
+    "sint32": 1, "sint64": 1, "double": 2, "float": 3,
+    "fixed64": 4, "sfixed64": 4, "fixed32": 6, "sfixed32": 7,
+    "string": ENC_BYTES, "bytes": ENC_BYTES,
+}
+
+
+class EncodeSpec(NamedTuple):
+    """Field spec of the device encoder, fields in ascending field number.
+    ``slot[f]`` is field f's row in the int64 inputs (``int_fields``), the
+    float64 inputs (``float_fields``) or its string slot (``str_fields``),
+    whichever its kind reads."""
+    fno: List[int]
+    kind: List[int]
+    slot: List[int]
+    names: List[str]
+    int_fields: List[str]
+    float_fields: List[str]
+    str_fields: List[str]
+
+
+def build_encode_spec(schema: ProtoSchema, columns: Dict[str, Column]
+                      ) -> Optional[EncodeSpec]:
+    """Kernel field spec for encoding ``columns`` under ``schema``, or None
+    when the device encoder does not take this input and the host codec must:
+    a schema wider than PROTO_ENC_MAX_FIELDS, or a matched column of the
+    wrong kind (scalar fields need numeric columns, string/bytes fields
+    binary ones). A schema field with no column is absent from every row and
+    therefore from the spec. Residency is the caller's check
+    (``encode_device``)."""
+    if len(schema.fields) > PROTO_ENC_MAX_FIELDS:
+        return None
+    spec = EncodeSpec([], [], [], [], [], [], [])
+    for no in sorted(schema.fields):
+        name, t = schema.fields[no]
+        col = columns.get(name)
+        if col is None:
+            continue
+        k = _ENC_KIND[t]
+        if col.kind != ("binary" if k == ENC_BYTES else "numeric"):
+            return None
+        fields = spec.str_fields if k == ENC_BYTES else \
+            spec.float_fields if t in _FLOAT_TYPES else spec.int_fields
+        spec.fno.append(no)
+        spec.kind.append(k)
+        spec.slot.append(len(fields))
+        spec.names.append(name)
+        fields.append(name)
+    return spec
+
+
+def encode_device(schema: ProtoSchema, columns: Dict[str, Column]
+                  ) -> Optional[Tuple[EncodeSpec, torch.device]]:
+    """(spec, device) when the device encoder applies: the native extension
+    is loaded, ``build_encode_spec`` accepts the input and every matched
+    column is on the same GPU. None → host path."""
+    from .. import ops
+    spec = build_encode_spec(schema, columns)
+    if spec is None or not spec.fno or not ops.native_available():
+        return None
+    devices = set()
+    for name in spec.names:
+        col = columns[name]
+        devices.update(t.device for t in (col.data, col.offsets, col.validity)
+                       if t is not None)
+    if len(devices) != 1:
+        return None
+    device = devices.pop()
+    return (spec, device) if device.type == "cuda" else None
+
+
+def encode_rows_host(batch: MessageBatch, schema: ProtoSchema) -> List[bytes]:
+    """The per-row host encode: every column to the host, one dict per row,
+    ``encode_message`` on each."""
+    payloads = []
+    for r in batch.to_rows():
+        clean = {}
+        for name, (no, t) in schema.by_name.items():
+            v = r.get(name)
+            if isinstance(v, (bytes, bytearray)) and t == "string":
+                v = v.decode("utf-8", "replace")
+            clean[name] = v
+        payloads.append(encode_message(clean, schema))
+    return payloads
 
 
 class ProtobufToArrowProcessor(Processor):
@@ -145,23 +238,45 @@ class ProtobufToArrowProcessor(Processor):
         return out
 
 
+def load_encoder_choice(config: dict) -> str:
+    choice = config.get("encoder", "auto")
+    if choice not in ("auto", "host"):
+        raise ConfigError(
+            f"protobuf 'encoder' must be 'auto' or 'host', got {choice!r}")
+    return choice
+
+
 class ArrowToProtobufProcessor(Processor):
+    """Rows → one proto3 message each, in ``__value__``.
+
+    ``encoder: auto`` (default) encodes on the GPU (csrc/proto_encode.hip)
+    when the native extension is loaded, every schema-matched column is on
+    one device with the kind its field needs (numeric for scalar fields,
+    binary for string/bytes) and the schema has at most PROTO_ENC_MAX_FIELDS
+    fields; ``__value__`` then stays on that device. Every other input — host
+    batches, mixed residency, a kind mismatch, wider schemas — and
+    ``encoder: host`` take the per-row host codec and give a host-resident
+    ``__value__``. The bytes are the same either way, with one exception: the
+    device copies a ``string`` field's bytes as they are, while the host path
+    decodes them with ``errors="replace"`` and re-encodes, so input that is
+    not valid UTF-8 comes out with U+FFFD substitutions on the host and
+    untouched on the device. UTF-8 is not validated on the device.
+    """
+
     def __init__(self, config: dict, resource=None):
         self.schema = _load_schema(config)
+        self.encoder = load_encoder_choice(config)
 
     async def process(self, batch: MessageBatch) -> List[MessageBatch]:
         if batch.num_rows == 0:
             return []
-        rows = batch.to_rows()
-        payloads = []
-        for r in rows:
-            clean = {}
-            for name, (no, t) in self.schema.by_name.items():
-                v = r.get(name)
-                if isinstance(v, (bytes, bytearray)) and t == "string":
-                    v = v.decode("utf-8", "replace")
-                clean[name] = v
-            payloads.append(encode_message(clean, self.schema))
+        if self.encoder == "auto" and \
+                encode_device(self.schema, batch.columns) is not None:
+            from .. import ops
+            value = ops.proto_encode(batch, self.schema)
+            return [MessageBatch({DEFAULT_BINARY_VALUE_FIELD: value},
+                                 batch.input_name)]
+        payloads = encode_rows_host(batch, self.schema)
         return [MessageBatch.from_binary(payloads,
                                          input_name=batch.input_name)]
 
@@ -176,7 +291,9 @@ def _build_p2a(config: dict, resource=None) -> ProtobufToArrowProcessor:
 
 
 @register("processor", "arrow_to_protobuf",
-          description="Encode rows as scalar proto3 messages into __value__",
+          description="Encode rows as scalar proto3 messages into __value__ "
+                      "(GPU encode kernel for device-resident batches; "
+                      "encoder: auto | host)",
           example={"type": "arrow_to_protobuf",
                    "proto": "message M { double v = 1; }"})
 def _build_a2p(config: dict, resource=None) -> ArrowToProtobufProcessor:
