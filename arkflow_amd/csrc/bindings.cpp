@@ -910,9 +910,45 @@ hash_agg_capture(torch::Tensor keys, torch::Tensor nrow,
   return {uniq, counts_i64, red};
 }
 
+using StringColumns = std::vector<std::tuple<torch::Tensor, torch::Tensor>>;
+
+// String copy-out of a decoder. lens is the int32 [ns][n] lengths tensor its
+// parse kernel filled; per slot, offsets = exclusive cumsum of the lengths
+// (an absent value has length 0 → empty string). `head` holds the decoder's
+// own leading summary entries (int64, on the device): they and the slot
+// totals ride ONE concatenated readback, the batch's only device sync — the
+// earlier shape (err.item + validity .cpu + totals .to(CPU)) cost three
+// stream drains per batch and floored small-batch decode at ~0.2 ms. Then
+// launch(s, offs, out) fills slot s's `out` where its total is > 0.
+// Returns (per slot (data, offsets), summary = [head..., totals...] on host).
+template <typename Launch>
+std::tuple<StringColumns, torch::Tensor> copy_out_strings(
+    const torch::Tensor& lens, int64_t ns, int64_t n,
+    std::vector<torch::Tensor> head, Launch launch) {
+  if (n == 0) ns = 0;
+  int64_t lead = 0;
+  for (const auto& h : head) lead += h.numel();
+  std::vector<torch::Tensor> offs(std::max<int64_t>(ns, 0));
+  for (int64_t s = 0; s < ns; ++s) {
+    offs[s] = exclusive_offsets(lens[s].contiguous());
+    head.push_back(offs[s].narrow(0, n, 1));
+  }
+  auto summary = torch::cat(head).cpu();  // the one device sync
+  const int64_t* tot = summary.data_ptr<int64_t>() + lead;
+  StringColumns strings;
+  for (int64_t s = 0; s < ns; ++s) {
+    auto out = torch::empty({std::max<int64_t>(tot[s], 1)},
+                            lens.options().dtype(torch::kUInt8));
+    if (tot[s] > 0) launch(s, offs[s], out);
+    strings.emplace_back(out.slice(0, 0, tot[s]), offs[s]);
+  }
+  return {strings, summary};
+}
+
+// (out_f64, out_i64, found, err, strings, summary); summary = [err,
+// all_valid × max(nf, 1), string totals × n_str] on the host.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-           std::vector<std::tuple<torch::Tensor, torch::Tensor>>,
-           torch::Tensor>
+           StringColumns, torch::Tensor>
 json_decode(torch::Tensor data, torch::Tensor offsets,
             std::vector<std::string> names, std::vector<int64_t> kind,
             std::vector<int64_t> slot, int64_t n_int, int64_t n_float,
@@ -920,15 +956,18 @@ json_decode(torch::Tensor data, torch::Tensor offsets,
   check_cuda(data, "data");
   check_cuda(offsets, "offsets");
   int64_t n = offsets.numel() - 1;
-  int nf = (int)names.size();
-  std::vector<char> packed(nf * 24, 0);
-  std::vector<int> nl(nf), kd(nf), sl(nf), par(nf);
+  TORCH_CHECK(names.size() <= JSON_MAX_FIELDS, "json_decode takes at most ",
+              JSON_MAX_FIELDS, " fields, got ", names.size());
+  TORCH_CHECK(kind.size() == names.size() && slot.size() == names.size());
+  const int nf = (int)names.size();
+  JsonSpec spec{};
+  spec.nf = nf;
   // dotted names ("user.id") address one level of nesting: collect the
   // distinct parent segments, scope each field to its parent index
   std::vector<std::string> parents;
   for (int f = 0; f < nf; ++f) {
     std::string leaf = names[f];
-    par[f] = -1;
+    spec.parent[f] = -1;
     auto dot = leaf.find('.');
     if (dot != std::string::npos) {
       std::string parent = leaf.substr(0, dot);
@@ -939,47 +978,42 @@ json_decode(torch::Tensor data, torch::Tensor offsets,
       for (size_t q = 0; q < parents.size(); ++q)
         if (parents[q] == parent) pi = (int)q;
       if (pi < 0) {
+        TORCH_CHECK(parents.size() < JSON_MAX_PARENTS,
+                    "too many nested parents (max ", JSON_MAX_PARENTS, ")");
+        TORCH_CHECK(parent.size() < JSON_MAX_NAME,
+                    "json parent name too long");
+        pi = (int)parents.size();
         parents.push_back(parent);
-        pi = (int)parents.size() - 1;
+        memcpy(spec.parents[pi], parent.data(), parent.size());
+        spec.parent_len[pi] = (int)parent.size();
       }
-      par[f] = pi;
+      spec.parent[f] = pi;
     }
-    TORCH_CHECK(leaf.size() < 24, "json field name too long");
-    memcpy(&packed[f * 24], leaf.data(), leaf.size());
-    nl[f] = (int)leaf.size();
-    kd[f] = (int)kind[f];
-    sl[f] = (int)slot[f];
+    TORCH_CHECK(leaf.size() < JSON_MAX_NAME, "json field name too long");
+    memcpy(spec.names[f], leaf.data(), leaf.size());
+    spec.name_len[f] = (int)leaf.size();
+    const int64_t slots = kind[f] == 2 ? n_str : kind[f] == 1 ? n_float : n_int;
+    TORCH_CHECK(kind[f] >= 0 && kind[f] <= 2 && slot[f] >= 0 &&
+                    slot[f] < slots, "json field kind or slot out of range");
+    spec.kind[f] = (int)kind[f];
+    spec.slot[f] = (int)slot[f];
   }
-  TORCH_CHECK(parents.size() <= 8, "too many nested parents (max 8)");
-  int np = (int)parents.size();
-  std::vector<char> ppacked(std::max(np, 1) * 24, 0);
-  std::vector<int> pl(std::max(np, 1), 0);
-  for (int q = 0; q < np; ++q) {
-    TORCH_CHECK(parents[q].size() < 24, "json parent name too long");
-    memcpy(&ppacked[q * 24], parents[q].data(), parents[q].size());
-    pl[q] = (int)parents[q].size();
-  }
-  auto out_f = torch::zeros({std::max<int64_t>(n_float, 1),
-                             std::max<int64_t>(n, 1)},
-                            data.options().dtype(torch::kFloat64));
-  auto out_i = torch::zeros({std::max<int64_t>(n_int, 1),
-                             std::max<int64_t>(n, 1)},
-                            data.options().dtype(torch::kInt64));
-  auto str_start = torch::zeros({std::max<int64_t>(n_str, 1),
-                                 std::max<int64_t>(n, 1)},
-                                data.options().dtype(torch::kInt64));
-  auto str_ulen = torch::zeros({std::max<int64_t>(n_str, 1),
-                                std::max<int64_t>(n, 1)},
-                               data.options().dtype(torch::kInt32));
-  auto found = torch::zeros({std::max(nf, 1), std::max<int64_t>(n, 1)},
-                            data.options().dtype(torch::kUInt8));
+  spec.np = (int)parents.size();
+  auto rows = [&](int64_t r, torch::ScalarType t) {
+    return torch::zeros({std::max<int64_t>(r, 1), std::max<int64_t>(n, 1)},
+                        data.options().dtype(t));
+  };
+  auto out_f = rows(n_float, torch::kFloat64);
+  auto out_i = rows(n_int, torch::kInt64);
+  auto str_start = rows(n_str, torch::kInt64);
+  auto str_ulen = rows(n_str, torch::kInt32);
+  auto found = rows(nf, torch::kUInt8);
   auto err = torch::zeros({1}, data.options().dtype(torch::kInt32));
   auto found_count = torch::zeros({std::max(nf, 1)},
                                   data.options().dtype(torch::kInt32));
   if (n > 0)
-    launch_json_decode(data.data_ptr<uint8_t>(), offsets.data_ptr<int64_t>(),
-                       n, nf, packed.data(), nl.data(), kd.data(), sl.data(),
-                       par.data(), np, ppacked.data(), pl.data(),
+    launch_json_decode(&spec, data.data_ptr<uint8_t>(),
+                       offsets.data_ptr<int64_t>(), n,
                        out_f.data_ptr<double>(), out_i.data_ptr<int64_t>(),
                        str_start.data_ptr<int64_t>(),
                        str_ulen.data_ptr<int32_t>(),
@@ -989,58 +1023,30 @@ json_decode(torch::Tensor data, torch::Tensor offsets,
                        // scans dwarf the per-doc state machine (which the
                        // thread-per-doc kernel amortizes 64 docs/wave):
                        // measured crossover is in the multi-KB range
-                       (int)(n > 0 && data.numel() / n >= 2048),
-                       cur_stream());
-  // string copy-out: per field, offsets = exclusive cumsum of unescaped
-  // lengths; one host sync for ALL totals at once, then one copy kernel per
-  // string field (ulen of absent docs is 0 → empty strings, validity=found)
-  std::vector<std::tuple<torch::Tensor, torch::Tensor>> strings;
-  // ONE host readback for err + per-field all-valid + string totals — the
-  // previous shape (err.item + validity .cpu + totals .to(CPU)) cost three
-  // stream drains per batch and floored small-batch decode at ~0.2 ms
-  std::vector<torch::Tensor> sumv;
-  sumv.push_back(err.to(torch::kInt64));
-  // all_valid[f] ⇔ found_count[f] == n (counts accumulated in-kernel —
-  // a found.min(dim=1) reduce cost ~40 µs/batch)
-  sumv.push_back((found_count.to(torch::kInt64) ==
-                  torch::full({std::max(nf, 1)}, n,
-                              torch::dtype(torch::kInt64)
-                                  .device(data.device())))
-                     .to(torch::kInt64));
-  std::vector<torch::Tensor> offs(std::max<int64_t>(n_str, 0));
-  if (n_str > 0 && n > 0) {
-    for (int64_t s = 0; s < n_str; ++s) {
-      offs[s] = exclusive_offsets(str_ulen[s].contiguous());
-      sumv.push_back(offs[s].narrow(0, n, 1));
-    }
-  }
-  auto summary = torch::cat(sumv).cpu();  // the one device sync
-  if (n_str > 0 && n > 0) {
-    auto* tot = summary.data_ptr<int64_t>() + 1 + std::max(nf, 1);
-    for (int64_t s = 0; s < n_str; ++s) {
-      auto out = torch::empty({std::max<int64_t>(tot[s], 1)},
-                              data.options().dtype(torch::kUInt8));
-      // found row for this slot: find the field index with this slot
-      int frow = 0;
-      for (int f = 0; f < nf; ++f)
-        if (kd[f] == 2 && sl[f] == (int)s) frow = f;
-      if (tot[s] > 0) {
+                       (int)(data.numel() / n >= 2048), cur_stream());
+  // all_valid[f] ⇔ found_count[f] == n (counts accumulated in-kernel — a
+  // found.min(dim=1) reduce cost ~40 µs/batch); validity = found
+  auto all_valid = (found_count.to(torch::kInt64) ==
+                    torch::full({std::max(nf, 1)}, n,
+                                torch::dtype(torch::kInt64)
+                                    .device(data.device())))
+                       .to(torch::kInt64);
+  auto [strings, summary] = copy_out_strings(
+      str_ulen, n_str, n, {err.to(torch::kInt64), all_valid},
+      [&](int64_t s, const torch::Tensor& offs, torch::Tensor& out) {
+        // found row for this slot: the field index with this slot
+        int frow = 0;
+        for (int f = 0; f < nf; ++f)
+          if (spec.kind[f] == 2 && spec.slot[f] == (int)s) frow = f;
         // wave-per-doc for long strings (coalesced fast path); the
         // thread-per-doc kernel stays ahead when strings are tiny
-        if (tot[s] / n >= 32)
-          launch_json_copy_strings_wave(
-              data.data_ptr<uint8_t>(), str_start[s].data_ptr<int64_t>(),
-              offs[s].data_ptr<int64_t>(), found[frow].data_ptr<uint8_t>(),
-              n, data.numel(), out.data_ptr<uint8_t>(), cur_stream());
-        else
-          launch_json_copy_strings(
-              data.data_ptr<uint8_t>(), str_start[s].data_ptr<int64_t>(),
-              offs[s].data_ptr<int64_t>(), found[frow].data_ptr<uint8_t>(),
-              n, data.numel(), out.data_ptr<uint8_t>(), cur_stream());
-      }
-      strings.emplace_back(out.slice(0, 0, tot[s]), offs[s]);
-    }
-  }
+        auto* copy = out.numel() / n >= 32  // out holds the slot's total
+                         ? launch_json_copy_strings_wave
+                         : launch_json_copy_strings;
+        copy(data.data_ptr<uint8_t>(), str_start[s].data_ptr<int64_t>(),
+             offs.data_ptr<int64_t>(), found[frow].data_ptr<uint8_t>(), n,
+             data.numel(), out.data_ptr<uint8_t>(), cur_stream());
+      });
   return {out_f, out_i, found, err, strings, summary};
 }
 
@@ -1096,8 +1102,10 @@ torch::Tensor bytes_hash(torch::Tensor data, torch::Tensor offsets) {
   return out;
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor,
-           std::vector<std::tuple<torch::Tensor, torch::Tensor>>,
+// (out_i64, out_f64, err, strings, summary); summary = [err, string totals ×
+// n_str] on the host, empty in capture mode. is_float[f] repeats what kind[f]
+// says (F64/F32 → the float64 outputs) and is only checked against it.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, StringColumns,
            torch::Tensor>
 proto_decode(
     torch::Tensor data, torch::Tensor offsets,
@@ -1109,63 +1117,61 @@ proto_decode(
   TORCH_CHECK(data.scalar_type() == torch::kUInt8);
   TORCH_CHECK(offsets.scalar_type() == torch::kInt64);
   int64_t n = offsets.numel() - 1;
-  int nf = (int)fno.size();
-  std::vector<int> f(nf), k(nf), isf(nf), sl(nf);
-  for (int i = 0; i < nf; ++i) {
-    f[i] = (int)fno[i]; k[i] = (int)kind[i];
-    isf[i] = (int)is_float[i]; sl[i] = (int)slot[i];
+  const size_t nf = fno.size();
+  TORCH_CHECK(nf <= PROTO_MAX_FIELDS, "proto_decode takes at most ",
+              PROTO_MAX_FIELDS, " fields, got ", nf);
+  TORCH_CHECK(kind.size() == nf && is_float.size() == nf && slot.size() == nf);
+  ProtoSpec spec{};
+  spec.nf = (int)nf;
+  for (size_t f = 0; f < nf; ++f) {
+    const int64_t k = kind[f];
+    const bool flt = k == PROTO_F64 || k == PROTO_F32;
+    int64_t slots;
+    switch (k) {
+      case PROTO_VARINT: case PROTO_ZIGZAG: case PROTO_FIXED64:
+      case PROTO_FIXED32: case PROTO_SFIXED32: slots = n_int; break;
+      case PROTO_F64: case PROTO_F32: slots = n_float; break;
+      case PROTO_BYTES: slots = n_str; break;
+      default: TORCH_CHECK(false, "unknown proto_decode kind ", k);
+    }
+    TORCH_CHECK((is_float[f] != 0) == flt, "is_float disagrees with kind");
+    TORCH_CHECK(slot[f] >= 0 && slot[f] < slots, "field slot out of range");
+    spec.fno[f] = (int)fno[f];
+    spec.kind[f] = (int)k;
+    spec.slot[f] = (int)slot[f];
   }
-  auto out_i = torch::zeros({std::max<int64_t>(n_int, 1), std::max<int64_t>(n, 1)},
-                            data.options().dtype(torch::kInt64));
-  auto out_f = torch::zeros({std::max<int64_t>(n_float, 1), std::max<int64_t>(n, 1)},
-                            data.options().dtype(torch::kFloat64));
-  auto str_start = torch::zeros({std::max<int64_t>(n_str, 1),
-                                 std::max<int64_t>(n, 1)},
-                                data.options().dtype(torch::kInt64));
-  auto str_len = torch::zeros({std::max<int64_t>(n_str, 1),
-                               std::max<int64_t>(n, 1)},
-                              data.options().dtype(torch::kInt32));
+  auto rows = [&](int64_t r, torch::ScalarType t) {
+    return torch::zeros({std::max<int64_t>(r, 1), std::max<int64_t>(n, 1)},
+                        data.options().dtype(t));
+  };
+  auto out_i = rows(n_int, torch::kInt64);
+  auto out_f = rows(n_float, torch::kFloat64);
+  auto str_start = rows(n_str, torch::kInt64);
+  auto str_len = rows(n_str, torch::kInt32);
   auto err = torch::zeros({1}, data.options().dtype(torch::kInt32));
   if (n > 0)
-    launch_proto_decode(data.data_ptr<uint8_t>(), offsets.data_ptr<int64_t>(),
-                        n, nf, f.data(), k.data(), isf.data(), sl.data(),
+    launch_proto_decode(&spec, data.data_ptr<uint8_t>(),
+                        offsets.data_ptr<int64_t>(), n,
                         out_i.data_ptr<int64_t>(), out_f.data_ptr<double>(),
                         str_start.data_ptr<int64_t>(),
                         str_len.data_ptr<int32_t>(), err.data_ptr<int32_t>(),
                         cur_stream());
-  // string/bytes copy-out (proto3 missing field → len 0 → empty value);
-  // err + totals ride ONE host readback (JSON decode learned the same —
-  // each extra sync floored small-batch decode)
-  std::vector<std::tuple<torch::Tensor, torch::Tensor>> strings;
   if (capture) {
     // hipGraph capture: no host syncs allowed — string fields (which need
     // a totals readback for allocation) are unsupported; the caller
     // validates err outside the capture
     TORCH_CHECK(n_str == 0, "capture-mode proto decode cannot have strings");
-    return {out_i, out_f, err, strings, torch::empty({0})};
+    return {out_i, out_f, err, StringColumns{}, torch::empty({0})};
   }
-  std::vector<torch::Tensor> sumv = {err.to(torch::kInt64)};
-  std::vector<torch::Tensor> offs(std::max<int64_t>(n_str, 0));
-  if (n_str > 0 && n > 0) {
-    for (int64_t s = 0; s < n_str; ++s) {
-      offs[s] = exclusive_offsets(str_len[s].contiguous());
-      sumv.push_back(offs[s].narrow(0, n, 1));
-    }
-  }
-  auto summary = torch::cat(sumv).cpu();
-  if (n_str > 0 && n > 0) {
-    auto* tot = summary.data_ptr<int64_t>() + 1;
-    for (int64_t s = 0; s < n_str; ++s) {
-      auto out = torch::empty({std::max<int64_t>(tot[s], 1)},
-                              data.options().dtype(torch::kUInt8));
-      if (tot[s] > 0)
+  // proto3 missing field → len 0 → empty value
+  auto [strings, summary] = copy_out_strings(
+      str_len, n_str, n, {err.to(torch::kInt64)},
+      [&](int64_t s, const torch::Tensor& offs, torch::Tensor& out) {
         launch_proto_copy_bytes(data.data_ptr<uint8_t>(),
                                 str_start[s].data_ptr<int64_t>(),
-                                offs[s].data_ptr<int64_t>(), n,
+                                offs.data_ptr<int64_t>(), n,
                                 out.data_ptr<uint8_t>(), cur_stream());
-      strings.emplace_back(out.slice(0, 0, tot[s]), offs[s]);
-    }
-  }
+      });
   return {out_i, out_f, err, strings, summary};
 }
 
@@ -1219,14 +1225,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> proto_encode(
     int wire;
     int64_t slots;
     switch (k) {
-      case PROTO_ENC_VARINT: case PROTO_ENC_ZIGZAG:
+      case PROTO_VARINT: case PROTO_ZIGZAG:
         wire = 0; slots = in_i64.size(0); break;
-      case PROTO_ENC_FIXED64: wire = 1; slots = in_i64.size(0); break;
-      case PROTO_ENC_FIXED32: case PROTO_ENC_SFIXED32:
+      case PROTO_FIXED64: wire = 1; slots = in_i64.size(0); break;
+      case PROTO_FIXED32: case PROTO_SFIXED32:
         wire = 5; slots = in_i64.size(0); break;
-      case PROTO_ENC_F64: wire = 1; slots = in_f64.size(0); break;
-      case PROTO_ENC_F32: wire = 5; slots = in_f64.size(0); break;
-      case PROTO_ENC_BYTES: wire = 2; slots = (int64_t)strings.size(); break;
+      case PROTO_F64: wire = 1; slots = in_f64.size(0); break;
+      case PROTO_F32: wire = 5; slots = in_f64.size(0); break;
+      case PROTO_BYTES: wire = 2; slots = (int64_t)strings.size(); break;
       default: TORCH_CHECK(false, "unknown proto_encode kind ", k);
     }
     TORCH_CHECK(slot[f] >= 0 && slot[f] < slots, "field slot out of range");

@@ -45,30 +45,43 @@ struct AttnArgs {
 // kernel; else nothing is launched and -1 is returned. 0 otherwise.
 int launch_attention_bf16(const AttnArgs* args);
 
+// ---- proto_decode.hip, proto_encode.hip ------------------------------------
+// Wire form of a scalar proto3 field, for the decoder and the encoder alike.
+// Integer kinds live in int64 columns, F64/F32 in float64 columns.
+enum ProtoKind {
+  PROTO_VARINT = 0,    // int32/int64/uint32/uint64/bool
+  PROTO_ZIGZAG = 1,    // sint32/sint64
+  PROTO_F64 = 2,       // double
+  PROTO_F32 = 3,       // float: encode rounds the float64 input to float32
+  PROTO_FIXED64 = 4,   // fixed64/sfixed64: the int64's 8 bytes
+  PROTO_FIXED32 = 6,   // fixed32: zero-extended; errors outside [0, 2^32)
+  PROTO_SFIXED32 = 7,  // sfixed32: sign-extended; errors outside [-2^31, 2^31)
+  PROTO_BYTES = 9,     // string/bytes
+};
+
 // ---- proto_decode.hip -------------------------------------------------------
+#define PROTO_MAX_FIELDS 16
+// Filled by the binding, passed to the kernel by value.
+struct ProtoSpec {
+  int nf;                      // <= PROTO_MAX_FIELDS
+  int fno[PROTO_MAX_FIELDS];   // field number
+  int kind[PROTO_MAX_FIELDS];  // ProtoKind
+  // row of out_f64 (F64, F32) / out_i64 (integer kinds), or the string slot
+  int slot[PROTO_MAX_FIELDS];
+};
 void launch_proto_copy_bytes(const uint8_t* data, const int64_t* start,
                              const int64_t* out_offs, int64_t n_msgs,
                              uint8_t* out, hipStream_t st);
-void launch_proto_decode(const uint8_t* data, const int64_t* offsets,
-                         int64_t n_msgs, int nf, const int* fno,
-                         const int* kind, const int* is_float,
-                         const int* slot, int64_t* out_i64, double* out_f64,
+// err_flags[0] is set to 1 for a varint longer than 10 bytes, a fixed or
+// length-delimited field running past its message, or wire type 3/4/6/7.
+void launch_proto_decode(const ProtoSpec* spec, const uint8_t* data,
+                         const int64_t* offsets, int64_t n_msgs,
+                         int64_t* out_i64, double* out_f64,
                          int64_t* str_start, int32_t* str_len,
                          int32_t* err_flags, hipStream_t st);
 
 // ---- proto_encode.hip -------------------------------------------------------
 #define PROTO_ENC_MAX_FIELDS 32
-// wire forms of a field; values 0..7 match launch_proto_decode's kinds
-enum ProtoEncKind {
-  PROTO_ENC_VARINT = 0,    // int32/int64/uint32/uint64/bool
-  PROTO_ENC_ZIGZAG = 1,    // sint32/sint64
-  PROTO_ENC_F64 = 2,       // double
-  PROTO_ENC_F32 = 3,       // float: the float64 input rounded to float32
-  PROTO_ENC_FIXED64 = 4,   // fixed64/sfixed64: the int64's 8 bytes
-  PROTO_ENC_FIXED32 = 6,   // fixed32: error outside [0, 2^32)
-  PROTO_ENC_SFIXED32 = 7,  // sfixed32: error outside [-2^31, 2^31)
-  PROTO_ENC_BYTES = 9,     // string/bytes
-};
 // Fields in ascending field number; a schema field with no input column is
 // simply not listed. Passed to the kernels by value.
 struct ProtoEncSpec {
@@ -77,7 +90,7 @@ struct ProtoEncSpec {
   int prefix_len;                          // <= 8
   uint8_t prefix[8];                       // written at the start of each row
   uint32_t tag[PROTO_ENC_MAX_FIELDS];      // (field number << 3) | wire type
-  uint8_t kind[PROTO_ENC_MAX_FIELDS];      // ProtoEncKind
+  uint8_t kind[PROTO_ENC_MAX_FIELDS];      // ProtoKind
   // row of in_i64 (integer kinds) / in_f64 (F64, F32), or the string slot
   uint8_t slot[PROTO_ENC_MAX_FIELDS];
   const uint8_t* valid[PROTO_ENC_MAX_FIELDS];  // uint8[n], or null: no NULLs
@@ -104,12 +117,26 @@ void launch_proto_encode_copy(const ProtoEncSpec* spec, int64_t n,
                               int64_t out_len, hipStream_t st);
 
 // ---- json_decode.hip --------------------------------------------------------
-void launch_json_decode(const uint8_t* data, const int64_t* offsets,
-                        int64_t n_docs, int nf, const char* names,
-                        const int* name_len, const int* kind, const int* slot,
-                        const int* parent, int np, const char* parents,
-                        const int* parent_len, double* out_f64,
-                        int64_t* out_i64, int64_t* str_start,
+#define JSON_MAX_FIELDS 16
+#define JSON_MAX_PARENTS 8
+#define JSON_MAX_NAME 24  // names are shorter than this
+// Filled by the binding, passed to the kernels by value. A dotted schema name
+// ("user.id") is the leaf "id" scoped to the parent object "user".
+struct JsonSpec {
+  int nf;  // <= JSON_MAX_FIELDS
+  char names[JSON_MAX_FIELDS][JSON_MAX_NAME];  // leaf names
+  int name_len[JSON_MAX_FIELDS];
+  int kind[JSON_MAX_FIELDS];  // 0 → out_i64 (ints+bools), 1 → out_f64, 2 → str
+  int slot[JSON_MAX_FIELDS];
+  int parent[JSON_MAX_FIELDS];  // -1 = top level, else index into parents
+  int np;                       // <= JSON_MAX_PARENTS
+  char parents[JSON_MAX_PARENTS][JSON_MAX_NAME];
+  int parent_len[JSON_MAX_PARENTS];
+};
+// use_wave: one wave per document instead of one thread
+void launch_json_decode(const JsonSpec* spec, const uint8_t* data,
+                        const int64_t* offsets, int64_t n_docs,
+                        double* out_f64, int64_t* out_i64, int64_t* str_start,
                         int32_t* str_ulen, uint8_t* found, int32_t* err,
                         int32_t* found_count, int use_wave, hipStream_t st);
 void launch_json_copy_strings(const uint8_t* data, const int64_t* start,

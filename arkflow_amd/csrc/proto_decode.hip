@@ -3,22 +3,13 @@
 // (data + offsets) into columnar outputs — the survey's "warp-per-message
 // varint decode kernel writing columnar" mapping for the reference's
 // protobuf_to_arrow processor (crates/arkflow-plugin/src/processor/
-// protobuf.rs — scalar proto3 only). String fields are skipped here (host
-// path handles them); numeric-only schemas stay fully on-device.
+// protobuf.rs — scalar proto3 only). Numeric fields land in typed columns;
+// string/bytes fields record their span here and proto_copy_bytes_kernel
+// copies them out into a binary column, so every schema of at most
+// PROTO_MAX_FIELDS fields stays fully on-device.
 #include "common.h"
 #include "kernels_api.h"
-
-#define PROTO_MAX_FIELDS 16
-
-// kind: 0 varint, 1 zigzag, 2 f64, 3 f32, 4 u64(fixed), 5 i64(sfixed),
-//       6 u32(fixed), 7 i32(sfixed), 8 bool, 9 string/bytes (span record)
-struct ProtoSpec {
-  int nf;
-  int fno[PROTO_MAX_FIELDS];
-  int kind[PROTO_MAX_FIELDS];
-  int is_float[PROTO_MAX_FIELDS];  // 1 → out_f64 slot, 0 → out_i64 slot
-  int slot[PROTO_MAX_FIELDS];
-};
+#include "proto_wire.h"
 
 __global__ void proto_decode_kernel(const uint8_t* __restrict__ data,
                                     const int64_t* __restrict__ offsets,
@@ -33,17 +24,12 @@ __global__ void proto_decode_kernel(const uint8_t* __restrict__ data,
   for (; i < n_msgs; i += stride) {
     int64_t pos = offsets[i];
     const int64_t end = offsets[i + 1];
-    // proto3 defaults
+    // proto3 defaults: the outputs start zeroed
     while (pos < end) {
-      // read tag varint
-      uint64_t tag = 0;
-      int shift = 0;
-      while (pos < end) {
-        uint8_t b = data[pos++];
-        tag |= (uint64_t)(b & 0x7F) << shift;
-        if (!(b & 0x80)) break;
-        shift += 7;
-        if (shift > 63) { err_flags[0] = 1; return; }
+      uint64_t tag;
+      if (!proto_read_varint(data, &pos, end, &tag)) {
+        err_flags[0] = 1;
+        return;
       }
       int fno = (int)(tag >> 3);
       int wt = (int)(tag & 7);
@@ -54,37 +40,29 @@ __global__ void proto_decode_kernel(const uint8_t* __restrict__ data,
         if (f < spec.nf && spec.fno[f] == fno) fi = f;
       uint64_t raw = 0;
       if (wt == 0) {
-        int s2 = 0;
-        while (pos < end) {
-          uint8_t b = data[pos++];
-          raw |= (uint64_t)(b & 0x7F) << s2;
-          if (!(b & 0x80)) break;
-          s2 += 7;
-          if (s2 > 63) { err_flags[0] = 1; return; }
+        if (!proto_read_varint(data, &pos, end, &raw)) {
+          err_flags[0] = 1;
+          return;
         }
       } else if (wt == 1) {
         if (pos + 8 > end) { err_flags[0] = 1; return; }
-#pragma unroll
-        for (int b = 0; b < 8; ++b) raw |= (uint64_t)data[pos + b] << (8 * b);
+        raw = proto_load_le<8>(data, pos);
         pos += 8;
       } else if (wt == 5) {
         if (pos + 4 > end) { err_flags[0] = 1; return; }
-#pragma unroll
-        for (int b = 0; b < 4; ++b) raw |= (uint64_t)data[pos + b] << (8 * b);
+        raw = proto_load_le<4>(data, pos);
         pos += 4;
       } else if (wt == 2) {
         // length-delimited: string/bytes fields record their span for the
-        // copy-out pass; other wt==2 payloads are skipped
-        uint64_t ln = 0;
-        int s2 = 0;
-        while (pos < end) {
-          uint8_t b = data[pos++];
-          ln |= (uint64_t)(b & 0x7F) << s2;
-          if (!(b & 0x80)) break;
-          s2 += 7;
+        // copy-out pass; other wt==2 payloads are skipped. Compared unsigned:
+        // a length of 2^63 or more must not turn negative and pass.
+        uint64_t ln;
+        if (!proto_read_varint(data, &pos, end, &ln) ||
+            ln > (uint64_t)(end - pos)) {
+          err_flags[0] = 1;
+          return;
         }
-        if (pos + (int64_t)ln > end) { err_flags[0] = 1; return; }
-        if (fi >= 0 && spec.kind[fi] == 9) {
+        if (fi >= 0 && spec.kind[fi] == PROTO_BYTES) {
           str_start[(int64_t)spec.slot[fi] * n_msgs + i] = pos;
           str_len[(int64_t)spec.slot[fi] * n_msgs + i] = (int32_t)ln;
         }
@@ -95,27 +73,25 @@ __global__ void proto_decode_kernel(const uint8_t* __restrict__ data,
         return;
       }
       if (fi < 0) continue;
-      int kind = spec.kind[fi];
-      if (spec.is_float[fi]) {
-        double v;
-        if (kind == 2) {
-          v = __longlong_as_double((long long)raw);
-        } else if (kind == 3) {
-          v = (double)__uint_as_float((uint32_t)raw);
-        } else {
-          v = (double)raw;
-        }
-        out_f64[(int64_t)spec.slot[fi] * n_msgs + i] = v;
-      } else {
-        int64_t v;
-        switch (kind) {
-          case 1: v = (int64_t)((raw >> 1) ^ (~(raw & 1) + 1)); break;
-          case 5: v = (int64_t)raw; break;
-          case 7: v = (int64_t)(int32_t)(uint32_t)raw; break;
-          case 8: v = raw ? 1 : 0; break;
-          case 0: default: v = (int64_t)raw; break;
-        }
-        out_i64[(int64_t)spec.slot[fi] * n_msgs + i] = v;
+      const int64_t o = (int64_t)spec.slot[fi] * n_msgs + i;
+      switch (spec.kind[fi]) {
+        case PROTO_F64:
+          out_f64[o] = __longlong_as_double((long long)raw);
+          break;
+        case PROTO_F32:
+          out_f64[o] = (double)__uint_as_float((uint32_t)raw);
+          break;
+        case PROTO_ZIGZAG:
+          out_i64[o] = (int64_t)((raw >> 1) ^ (~(raw & 1) + 1));
+          break;
+        case PROTO_SFIXED32:
+          out_i64[o] = (int64_t)(int32_t)(uint32_t)raw;
+          break;
+        case PROTO_BYTES:  // a string field sent with a scalar wire type
+          break;
+        default:  // PROTO_VARINT, PROTO_FIXED64, PROTO_FIXED32
+          out_i64[o] = (int64_t)raw;
+          break;
       }
     }
   }
@@ -142,33 +118,20 @@ extern "C" {
 void launch_proto_copy_bytes(const uint8_t* data, const int64_t* start,
                              const int64_t* out_offs, int64_t n_msgs,
                              uint8_t* out, hipStream_t st) {
-  int grid = (int)((n_msgs + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) return;
-  proto_copy_bytes_kernel<<<grid, 256, 0, st>>>(data, start, out_offs, n_msgs,
-                                                out);
+  if (n_msgs < 1) return;
+  proto_copy_bytes_kernel<<<capped_grid(n_msgs), 256, 0, st>>>(
+      data, start, out_offs, n_msgs, out);
 }
 
-void launch_proto_decode(const uint8_t* data, const int64_t* offsets,
-                         int64_t n_msgs, int nf, const int* fno,
-                         const int* kind, const int* is_float,
-                         const int* slot, int64_t* out_i64, double* out_f64,
+void launch_proto_decode(const ProtoSpec* spec, const uint8_t* data,
+                         const int64_t* offsets, int64_t n_msgs,
+                         int64_t* out_i64, double* out_f64,
                          int64_t* str_start, int32_t* str_len,
                          int32_t* err_flags, hipStream_t st) {
-  ProtoSpec spec{};
-  spec.nf = nf > PROTO_MAX_FIELDS ? PROTO_MAX_FIELDS : nf;
-  for (int i = 0; i < spec.nf; ++i) {
-    spec.fno[i] = fno[i];
-    spec.kind[i] = kind[i];
-    spec.is_float[i] = is_float[i];
-    spec.slot[i] = slot[i];
-  }
-  int grid = (int)((n_msgs + 255) / 256);
-  if (grid > 2048) grid = 2048;
-  if (grid < 1) return;
-  proto_decode_kernel<<<grid, 256, 0, st>>>(data, offsets, n_msgs, spec,
-                                            out_i64, out_f64, str_start,
-                                            str_len, err_flags);
+  if (n_msgs < 1) return;
+  proto_decode_kernel<<<capped_grid(n_msgs), 256, 0, st>>>(
+      data, offsets, n_msgs, *spec, out_i64, out_f64, str_start, str_len,
+      err_flags);
 }
 
 }  // extern "C"

@@ -79,7 +79,7 @@ DEV_INLINE int64_t encode_row(const ProtoEncSpec& spec,
     const int sl = spec.slot[f];
     const uint8_t* valid = spec.valid[f];
     const bool present = !valid || valid[i];
-    if (kind == PROTO_ENC_BYTES) {
+    if (kind == PROTO_BYTES) {
       int64_t start = 0;
       const int64_t len = present ? str_span(spec, sl, i, &start, err) : 0;
       if (len == 0) {
@@ -93,11 +93,11 @@ DEV_INLINE int64_t encode_row(const ProtoEncSpec& spec,
       continue;
     }
     if (!present) continue;
-    if (kind == PROTO_ENC_F64 || kind == PROTO_ENC_F32) {
+    if (kind == PROTO_F64 || kind == PROTO_F32) {
       const double v = in_f64[(int64_t)sl * n + i];
       if (v == 0.0) continue;  // ±0.0; NaN compares unequal and is written
       sink.varint(spec.tag[f]);
-      if (kind == PROTO_ENC_F64) {
+      if (kind == PROTO_F64) {
         sink.fixed((uint64_t)__double_as_longlong(v), 8);
       } else {
         const float fv = (float)v;  // round to nearest even
@@ -110,21 +110,21 @@ DEV_INLINE int64_t encode_row(const ProtoEncSpec& spec,
     if (v == 0) continue;
     sink.varint(spec.tag[f]);
     switch (kind) {
-      case PROTO_ENC_ZIGZAG:
+      case PROTO_ZIGZAG:
         sink.varint(((uint64_t)v << 1) ^ (uint64_t)(v >> 63));
         break;
-      case PROTO_ENC_FIXED64:
+      case PROTO_FIXED64:
         sink.fixed((uint64_t)v, 8);
         break;
-      case PROTO_ENC_FIXED32:
+      case PROTO_FIXED32:
         if (v < 0 || v > 0xFFFFFFFFll) err[0] = 1;
         sink.fixed((uint64_t)v, 4);
         break;
-      case PROTO_ENC_SFIXED32:
+      case PROTO_SFIXED32:
         if (v < -2147483648ll || v > 2147483647ll) err[0] = 1;
         sink.fixed((uint64_t)v, 4);
         break;
-      case PROTO_ENC_VARINT:
+      case PROTO_VARINT:
       default:
         sink.varint((uint64_t)v);
         break;

@@ -25,6 +25,25 @@ from ..registry import register
 from ..spi import Processor
 
 
+# limits of the device decoder (csrc/kernels_api.h)
+JSON_MAX_FIELDS, JSON_MAX_PARENTS, JSON_MAX_NAME = 16, 8, 24
+
+
+def decode_on_device(schema: dict) -> bool:
+    """Whether the device decoder (csrc/json_decode.hip) takes this schema:
+    at most JSON_MAX_FIELDS fields under at most JSON_MAX_PARENTS distinct
+    parent objects, one nesting level, every leaf and parent name shorter
+    than JSON_MAX_NAME bytes. Any other schema is decoded on the host."""
+    parents = set()
+    for name in schema:
+        parts = name.split(".")
+        if len(parts) > 2 or \
+                any(len(p.encode()) >= JSON_MAX_NAME for p in parts):
+            return False
+        parents.update(parts[:-1])
+    return len(schema) <= JSON_MAX_FIELDS and len(parents) <= JSON_MAX_PARENTS
+
+
 def json_payloads_to_columns(payloads: List[bytes],
                              projection: Optional[List[str]] = None,
                              device=None) -> MessageBatch:
@@ -81,11 +100,12 @@ class JsonToArrowProcessor(Processor):
         self.device = torch.device(dev) if dev else getattr(
             resource, "device", None)
         self.keep_meta = bool(config.get("keep_meta", True))
-        # fixed-schema GPU fast path: {name: float|int|bool|str} decodes;
-        # dotted names ("user.id") extract one level of nesting on-device
+        # fixed-schema GPU fast path: {name: float|int|bool|str} decodes
         # on-device (csrc/json_decode.hip: scalar extraction + two-pass string
-        # copy-out with escape/\uXXXX handling); no schema → host pyarrow
-        # parse + inference
+        # copy-out with escape/\uXXXX handling); dotted names ("user.id")
+        # extract one level of nesting. A schema over the kernel's limits
+        # (decode_on_device) is decoded on the host instead; no schema → host
+        # pyarrow parse + inference
         self.schema = config.get("schema")
         if self.schema:
             for t in self.schema.values():
@@ -247,8 +267,11 @@ class JsonToArrowProcessor(Processor):
                 self._inferred = self._infer_schema(first)
             if self._inferred:
                 schema = self._inferred
-        if schema and col.data.is_cuda:
+        if schema and col.data.is_cuda and decode_on_device(schema):
             out = self._decode_gpu(col, schema)
+        elif schema and col.data.is_cuda:
+            # over the device decoder's limits: host parse, result returned
+            out = self._decode_host_schema(col, schema).to(col.data.device)
         elif schema:
             out = self._decode_host_schema(col, schema)
             if self.device is not None:

@@ -5,11 +5,13 @@ component/protobuf.rs: dynamic decode/encode of scalar proto3 fields from a
 .proto source (no nested/repeated/map/oneof — header :14-25). The decode hot
 path is a GPU kernel parsing the device-resident binary column directly
 (csrc/proto_decode.hip) — numeric fields into typed columns, string/bytes
-fields via a two-pass span-record + copy-out into binary columns. The encode
-hot path is its inverse (csrc/proto_encode.hip, through ops.proto_encode): a
-size pass, an offsets scan, a write pass and a wave-per-row payload copy turn
-device-resident columns into a device-resident ``__value__`` column, byte for
-byte what the host codec (proto_wire.encode_message) writes row by row.
+fields via a two-pass span-record + copy-out into binary columns; a schema of
+more than PROTO_MAX_FIELDS fields is decoded by the host codec instead. The
+encode hot path is its inverse (csrc/proto_encode.hip, through
+ops.proto_encode): a size pass, an offsets scan, a write pass and a
+wave-per-row payload copy turn device-resident columns into a device-resident
+``__value__`` column, byte for byte what the host codec
+(proto_wire.encode_message) writes row by row.
 """
 from __future__ import annotations
 
@@ -23,13 +25,18 @@ from ..registry import register
 from ..spi import Processor
 from .proto_wire import ProtoSchema, decode_message, encode_message
 
-_KIND_ENUM = {
-    "varint": 0, "zigzag": 1, "f64": 2, "f32": 3,
-    "u64": 4, "i64": 5, "u32": 6, "i32": 7,
+# ProtoKind of csrc/kernels_api.h by proto3 type: one table for the device
+# decoder and the device encoder
+KIND_BYTES = 9
+_KIND = {
+    "int32": 0, "int64": 0, "uint32": 0, "uint64": 0, "bool": 0,
+    "sint32": 1, "sint64": 1, "double": 2, "float": 3,
+    "fixed64": 4, "sfixed64": 4, "fixed32": 6, "sfixed32": 7,
+    "string": KIND_BYTES, "bytes": KIND_BYTES,
 }
 _FLOAT_TYPES = {"double", "float"}
-_INT_OUT = {"int32", "int64", "sint32", "sint64", "sfixed32", "sfixed64",
-            "bool"}
+PROTO_MAX_FIELDS = 16      # the device decoder's limit (csrc/kernels_api.h)
+PROTO_ENC_MAX_FIELDS = 32  # the device encoder's
 
 
 def _load_schema(config: dict) -> ProtoSchema:
@@ -42,6 +49,12 @@ def _load_schema(config: dict) -> ProtoSchema:
     return ProtoSchema.parse(src, config.get("message"))
 
 
+def decode_on_device(schema: ProtoSchema) -> bool:
+    """Whether the device decoder takes this schema: at most PROTO_MAX_FIELDS
+    fields. A wider one is decoded by the host codec."""
+    return len(schema.fields) <= PROTO_MAX_FIELDS
+
+
 def build_gpu_spec(schema):
     """Kernel field spec from a ProtoSchema: (fno, kind, isf, slot,
     int_fields, float_fields, str_fields) — shared by the processor and the
@@ -50,37 +63,16 @@ def build_gpu_spec(schema):
     int_fields, float_fields, str_fields = [], [], []
     for no in sorted(schema.fields):
         name, t = schema.fields[no]
+        # uint32/uint64/fixed stay in int64 (values < 2^63 in practice);
+        # only true floats go to the f64 output
+        fields = str_fields if _KIND[t] == KIND_BYTES else \
+            float_fields if t in _FLOAT_TYPES else int_fields
         fno.append(no)
-        if t in ("string", "bytes"):
-            kind.append(9)
-            isf.append(0)
-            slot.append(len(str_fields))
-            str_fields.append(name)
-        elif t in _FLOAT_TYPES:
-            kind.append(_KIND_ENUM["f64" if t == "double" else "f32"])
-            isf.append(1)
-            slot.append(len(float_fields))
-            float_fields.append(name)
-        else:
-            # uint32/uint64/fixed stay in int64 (values < 2^63 in
-            # practice); only true floats go to the f64 output
-            k = {"sint32": 1, "sint64": 1, "fixed64": 4, "sfixed64": 5,
-                 "fixed32": 6, "sfixed32": 7}.get(t, 0)
-            kind.append(k)
-            isf.append(0)
-            slot.append(len(int_fields))
-            int_fields.append(name)
+        kind.append(_KIND[t])
+        isf.append(int(t in _FLOAT_TYPES))
+        slot.append(len(fields))
+        fields.append(name)
     return fno, kind, isf, slot, int_fields, float_fields, str_fields
-
-
-PROTO_ENC_MAX_FIELDS = 32  # csrc/kernels_api.h
-ENC_BYTES = 9
-_ENC_KIND = {
-    "int32": 0, "int64": 0, "uint32": 0, "uint64": 0, "bool": 0,
-    "sint32": 1, "sint64": 1, "double": 2, "float": 3,
-    "fixed64": 4, "sfixed64": 4, "fixed32": 6, "sfixed32": 7,
-    "string": ENC_BYTES, "bytes": ENC_BYTES,
-}
 
 
 class EncodeSpec(NamedTuple):
@@ -114,10 +106,10 @@ def build_encode_spec(schema: ProtoSchema, columns: Dict[str, Column]
         col = columns.get(name)
         if col is None:
             continue
-        k = _ENC_KIND[t]
-        if col.kind != ("binary" if k == ENC_BYTES else "numeric"):
+        k = _KIND[t]
+        if col.kind != ("binary" if k == KIND_BYTES else "numeric"):
             return None
-        fields = spec.str_fields if k == ENC_BYTES else \
+        fields = spec.str_fields if k == KIND_BYTES else \
             spec.float_fields if t in _FLOAT_TYPES else spec.int_fields
         spec.fno.append(no)
         spec.kind.append(k)
@@ -176,10 +168,12 @@ class ProtobufToArrowProcessor(Processor):
         if col is None or col.kind != "binary":
             raise ProcessError(
                 f"protobuf_to_arrow: no binary column {self.value_field!r}")
-        if col.data.is_cuda:
-            out = self._decode_gpu(col)
-        else:
+        if not col.data.is_cuda:
             out = self._decode_cpu(col)
+        elif decode_on_device(self.schema):
+            out = self._decode_gpu(col)
+        else:  # over the device decoder's limit: host codec, result returned
+            out = self._decode_cpu(col).to(col.data.device)
         out.input_name = batch.input_name
         return [out]
 
