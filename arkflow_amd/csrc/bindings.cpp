@@ -671,6 +671,48 @@ std::vector<torch::Tensor> gather_columns(std::vector<torch::Tensor> cols,
   return gather_multi(cols, idx32, idx32.numel(), nullptr, {});
 }
 
+// Stable LSD radix sort of n > 0 unsigned keys by their low `npasses` bytes:
+// uint32 bits in an int32 tensor, or (wide) uint64 bits in an int64 tensor.
+// Returns (permutation, sorted keys).
+std::tuple<torch::Tensor, torch::Tensor> radix_sort_passes(torch::Tensor ka,
+                                                           bool wide,
+                                                           int npasses) {
+  int64_t n = ka.numel();
+  auto opts32 = ka.options().dtype(torch::kInt32);
+  auto st = cur_stream();
+  int nblocks = onesweep_nblocks(n);
+  auto hist = torch::empty({(int64_t)256 * nblocks}, opts32);
+  auto kb = torch::empty_like(ka);
+  auto idx_a = torch::arange(n, opts32);
+  auto idx_b = torch::empty({n}, opts32);
+  for (int p = 0; p < npasses; ++p) {
+    if (wide)
+      launch_os_hist256_u64((const uint64_t*)ka.data_ptr<int64_t>(), n,
+                            8 * p, hist.data_ptr<int32_t>(), nblocks, st);
+    else
+      launch_os_hist256_u32((const uint32_t*)ka.data_ptr<int32_t>(), n,
+                            8 * p, hist.data_ptr<int32_t>(), nblocks, st);
+    // one device scan turns bin-major block counts into global offsets
+    auto inc = hist.cumsum(0, torch::kInt32);
+    auto offs = (inc - hist).contiguous();
+    if (wide)
+      launch_onesweep_pass_u64((const uint64_t*)ka.data_ptr<int64_t>(),
+                               idx_a.data_ptr<int32_t>(),
+                               (uint64_t*)kb.data_ptr<int64_t>(),
+                               idx_b.data_ptr<int32_t>(), n, 8 * p,
+                               offs.data_ptr<int32_t>(), nblocks, st);
+    else
+      launch_onesweep_pass_u32((const uint32_t*)ka.data_ptr<int32_t>(),
+                               idx_a.data_ptr<int32_t>(),
+                               (uint32_t*)kb.data_ptr<int32_t>(),
+                               idx_b.data_ptr<int32_t>(), n, 8 * p,
+                               offs.data_ptr<int32_t>(), nblocks, st);
+    std::swap(ka, kb);
+    std::swap(idx_a, idx_b);
+  }
+  return {idx_a, ka};
+}
+
 torch::Tensor radix_argsort(torch::Tensor keys, bool descending) {
   // Onesweep: 8-bit digits + decoupled lookback, keys ping-ponged alongside
   // the permutation (radix_sort.hip onesweep_* kernels). f32/i32 → 4 chained
@@ -705,38 +747,110 @@ torch::Tensor radix_argsort(torch::Tensor keys, bool descending) {
   } else {
     TORCH_CHECK(false, "radix_argsort supports f32/i64/i32 keys");
   }
-  int npasses = wide ? 8 : 4;
-  int nblocks = onesweep_nblocks(n);
-  auto hist = torch::empty({(int64_t)256 * nblocks}, opts32);
-  auto kb = torch::empty_like(ka);
-  auto idx_a = torch::arange(n, opts32);
-  auto idx_b = torch::empty({n}, opts32);
-  for (int p = 0; p < npasses; ++p) {
-    if (wide)
-      launch_os_hist256_u64((const uint64_t*)ka.data_ptr<int64_t>(), n,
-                            8 * p, hist.data_ptr<int32_t>(), nblocks, st);
-    else
-      launch_os_hist256_u32((const uint32_t*)ka.data_ptr<int32_t>(), n,
-                            8 * p, hist.data_ptr<int32_t>(), nblocks, st);
-    // one device scan turns bin-major block counts into global offsets
-    auto inc = hist.cumsum(0, torch::kInt32);
-    auto offs = (inc - hist).contiguous();
-    if (wide)
-      launch_onesweep_pass_u64((const uint64_t*)ka.data_ptr<int64_t>(),
-                               idx_a.data_ptr<int32_t>(),
-                               (uint64_t*)kb.data_ptr<int64_t>(),
-                               idx_b.data_ptr<int32_t>(), n, 8 * p,
-                               offs.data_ptr<int32_t>(), nblocks, st);
-    else
-      launch_onesweep_pass_u32((const uint32_t*)ka.data_ptr<int32_t>(),
-                               idx_a.data_ptr<int32_t>(),
-                               (uint32_t*)kb.data_ptr<int32_t>(),
-                               idx_b.data_ptr<int32_t>(), n, 8 * p,
-                               offs.data_ptr<int32_t>(), nblocks, st);
-    std::swap(ka, kb);
-    std::swap(idx_a, idx_b);
+  return std::get<0>(radix_sort_passes(ka, wide, wide ? 8 : 4));
+}
+
+// ---------------------------------------------------------------- string order
+void check_binary(const torch::Tensor& data, const torch::Tensor& offsets) {
+  check_cuda(data, "data");
+  check_cuda(offsets, "offsets");
+  TORCH_CHECK(data.scalar_type() == torch::kUInt8, "data must be uint8");
+  TORCH_CHECK(offsets.scalar_type() == torch::kInt64 && offsets.numel() >= 1,
+              "offsets must be int64 with rows + 1 entries");
+}
+
+torch::Tensor bytes_compare_cols(torch::Tensor data_a, torch::Tensor offsets_a,
+                                 torch::Tensor data_b,
+                                 torch::Tensor offsets_b) {
+  check_binary(data_a, offsets_a);
+  check_binary(data_b, offsets_b);
+  int64_t n = offsets_a.numel() - 1;
+  TORCH_CHECK(offsets_b.numel() - 1 == n,
+              "bytes_compare: columns differ in row count");
+  auto out = torch::empty({n}, data_a.options().dtype(torch::kInt8));
+  launch_bytes_compare_cols(data_a.data_ptr<uint8_t>(),
+                            offsets_a.data_ptr<int64_t>(),
+                            data_b.data_ptr<uint8_t>(),
+                            offsets_b.data_ptr<int64_t>(), n,
+                            out.data_ptr<int8_t>(), cur_stream());
+  return out;
+}
+
+torch::Tensor bytes_compare_lit(torch::Tensor data, torch::Tensor offsets,
+                                std::string lit) {
+  check_binary(data, offsets);
+  int64_t n = offsets.numel() - 1;
+  auto out = torch::empty({n}, data.options().dtype(torch::kInt8));
+  if (n == 0) return out;
+  // 8 copies of the literal, copy s shifted s bytes into its 8-byte-aligned
+  // slab, so a row of any alignment has a copy it can compare by words
+  int64_t nl = (int64_t)lit.size();
+  int64_t slab = (nl + 8 + 7) / 8 * 8;
+  std::vector<uint8_t> host((size_t)(8 * slab), 0);
+  for (int s = 0; s < 8; ++s)
+    std::copy(lit.begin(), lit.end(), host.begin() + s * slab + s);
+  auto lit8 = torch::from_blob(host.data(), {8 * slab}, torch::kUInt8)
+                  .to(data.device());  // blocking: host outlives the copy
+  launch_bytes_compare_lit(data.data_ptr<uint8_t>(),
+                           offsets.data_ptr<int64_t>(), n,
+                           lit8.data_ptr<uint8_t>(), slab, nl,
+                           out.data_ptr<int8_t>(), cur_stream());
+  return out;
+}
+
+// Dense rank of the rows of a binary column: rank[i] = number of distinct
+// strings smaller than row i. Chunk-at-a-time refinement (bytes_order.hip):
+// per round two radix sorts over the open rows, a head-flag scan for the new
+// segment ids, and ONE scalar readback — the number of rows still open
+// (mask_to_indices sizes the next round with it).
+torch::Tensor bytes_rank(torch::Tensor data, torch::Tensor offsets) {
+  check_binary(data, offsets);
+  int64_t n = offsets.numel() - 1;
+  auto opts32 = offsets.options().dtype(torch::kInt32);
+  auto rank = torch::zeros({n}, offsets.options());
+  if (n <= 1) return rank;
+  TORCH_CHECK(n < (int64_t)1 << 30, "bytes_rank caps at 2^30 rows");
+  auto st = cur_stream();
+  auto perm = torch::arange(n, opts32);  // position -> row
+  auto seg = torch::zeros({n}, opts32);  // position -> dense segment id
+  auto head = torch::empty({n}, opts32);
+  auto pos = perm.clone();               // open positions, ascending
+  int seg_passes = 1;                    // radix bytes that hold an id < n
+  while (seg_passes < 4 && ((n - 1) >> (8 * seg_passes)) != 0) ++seg_passes;
+  const uint8_t* dptr = data.data_ptr<uint8_t>();
+  const int64_t* optr = offsets.data_ptr<int64_t>();
+  for (int64_t d = 0;; ++d) {
+    int64_t m = pos.numel();
+    auto key = torch::empty({m}, offsets.options());
+    auto row_o = torch::empty({m}, opts32);
+    auto seg_o = torch::empty({m}, opts32);
+    launch_bo_chunk_keys(dptr, optr, perm.data_ptr<int32_t>(),
+                         seg.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), m,
+                         d, (uint64_t*)key.data_ptr<int64_t>(),
+                         row_o.data_ptr<int32_t>(), seg_o.data_ptr<int32_t>(),
+                         st);
+    // stable sort by key, then by segment: segments keep their places and
+    // are ordered by key inside
+    auto [idx_a, key_a] = radix_sort_passes(key, /*wide=*/true, 8);
+    auto seg_a = torch::empty({m}, opts32);
+    launch_gather(seg_o.data_ptr(), idx_a.data_ptr<int32_t>(), m,
+                  seg_a.data_ptr(), 4, st);
+    auto [idx_b, seg_b] = radix_sort_passes(seg_a, /*wide=*/false, seg_passes);
+    auto open = torch::zeros({n}, offsets.options().dtype(torch::kBool));
+    launch_bo_apply_round(idx_a.data_ptr<int32_t>(), idx_b.data_ptr<int32_t>(),
+                          (const uint64_t*)key_a.data_ptr<int64_t>(),
+                          seg_b.data_ptr<int32_t>(), row_o.data_ptr<int32_t>(),
+                          pos.data_ptr<int32_t>(), m, perm.data_ptr<int32_t>(),
+                          head.data_ptr<int32_t>(), open.data_ptr<bool>(), st);
+    auto offs = exclusive_offsets(head);
+    launch_bo_segments(offs.data_ptr<int64_t>(), n, seg.data_ptr<int32_t>(),
+                       st);
+    pos = mask_to_indices(open);
+    if (pos.numel() == 0) break;
   }
-  return idx_a;
+  launch_bo_scatter_rank(perm.data_ptr<int32_t>(), seg.data_ptr<int32_t>(), n,
+                         rank.data_ptr<int64_t>(), st);
+  return rank;
 }
 
 // one-call C++ execution of `SELECT * FROM flow WHERE col OP literal`:
@@ -1452,6 +1566,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gather_columns", &gather_columns);
   m.def("gemm_bf16_variant", &gemm_bf16_variant);
   m.def("bytes_hash", &bytes_hash);
+  m.def("bytes_rank", &bytes_rank);
+  m.def("bytes_compare_cols", &bytes_compare_cols);
+  // Python bytes convert to std::string raw, as for bytes_match
+  m.def("bytes_compare_lit", &bytes_compare_lit);
   m.def("json_decode", &json_decode);
   m.def("fused_filter_gather", &fused_filter_gather);
   m.def("genfiltpack", &genfiltpack, py::arg("lo"), py::arg("width"),

@@ -1,7 +1,8 @@
 // Host-side interface of the relational kernels (WHERE, gather, GROUP BY,
-// join, ORDER BY, window frames and the scans between their passes). Included
-// by the .hip file that defines each launcher and by bindings.cpp, so a
-// declaration that drifts from its definition is a compile error.
+// join, ORDER BY, window frames, string order and the scans between their
+// passes). Included by the .hip file that defines each launcher and by
+// bindings.cpp, so a declaration that drifts from its definition is a compile
+// error.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -151,5 +152,34 @@ void launch_onesweep_pass_u64(const uint64_t* keys_in, const int32_t* idx_in,
                               uint64_t* keys_out, int32_t* idx_out, int64_t n,
                               int shift, const int32_t* block_offsets,
                               int nblocks, hipStream_t st);
+
+// ---- bytes_order.hip: three-way compare and dense rank of binary columns ----
+// out[i] = -1 / 0 / +1: row i of a against row i of b, bytewise unsigned, a
+// proper prefix first.
+void launch_bytes_compare_cols(const uint8_t* da, const int64_t* oa,
+                               const uint8_t* db, const int64_t* ob, int64_t n,
+                               int8_t* out, hipStream_t st);
+// Against one literal of nl bytes. lit8: 8 slabs of `slab` bytes (a multiple
+// of 8, at least nl + 8), slab s holding the literal from its byte s on.
+void launch_bytes_compare_lit(const uint8_t* da, const int64_t* oa, int64_t n,
+                              const uint8_t* lit8, int64_t slab, int64_t nl,
+                              int8_t* out, hipStream_t st);
+// One refinement round of the rank over the m open positions pos[0..m): keys
+// of byte chunk d, then (after the two sorts) rows, heads and open flags
+// written back. See the head of bytes_order.hip.
+void launch_bo_chunk_keys(const uint8_t* data, const int64_t* offsets,
+                          const int32_t* perm, const int32_t* seg,
+                          const int32_t* pos, int64_t m, int64_t d,
+                          uint64_t* key, int32_t* row_o, int32_t* seg_o,
+                          hipStream_t st);
+void launch_bo_apply_round(const int32_t* idx_a, const int32_t* idx_b,
+                           const uint64_t* key_a, const int32_t* seg_b,
+                           const int32_t* row_o, const int32_t* pos, int64_t m,
+                           int32_t* perm, int32_t* head, bool* open,
+                           hipStream_t st);
+void launch_bo_segments(const int64_t* offs, int64_t n, int32_t* seg,
+                        hipStream_t st);
+void launch_bo_scatter_rank(const int32_t* perm, const int32_t* seg, int64_t n,
+                            int64_t* rank, hipStream_t st);
 
 }  // extern "C"

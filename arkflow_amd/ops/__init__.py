@@ -153,8 +153,72 @@ def sort_indices(key: torch.Tensor, ascending: bool = True) -> torch.Tensor:
     return torch.argsort(key, stable=True, descending=not ascending)
 
 
+# --------------------------------------------------------------- string order
+# Order of binary columns: bytewise, unsigned, a proper prefix first — Python's
+# bytes order, SQLite's BINARY collation, code-point order for UTF-8.
+def _bytes_rows(col) -> list:
+    """Every row's bytes, NULL rows included (validity is the caller's)."""
+    data = col.data.detach().to("cpu").numpy().tobytes()
+    off = col.offsets.detach().to("cpu").tolist()
+    return [data[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def _check_binary(col, what: str):
+    if getattr(col, "kind", None) != "binary":
+        raise TypeError(f"{what} takes a binary Column")
+
+
+def bytes_rank(col) -> torch.Tensor:
+    """Dense rank of a binary column, int64[n]: rank[i] is the number of
+    distinct strings smaller than row i, so equal strings share a rank and
+    rank order is string order. NULL rows rank by whatever bytes they hold.
+
+    GPU: 7-byte chunk keys refined round by round over the radix argsort
+    (csrc/bytes_order.hip), one scalar readback per round. CPU: the plain
+    Python reference, sorted(set(rows)).
+    """
+    _check_binary(col, "bytes_rank")
+    if _use_native(col.data):
+        return require_native().bytes_rank(col.data.contiguous(),
+                                           col.offsets.contiguous())
+    rows = _bytes_rows(col)
+    order = {v: i for i, v in enumerate(sorted(set(rows)))}
+    return torch.tensor([order[v] for v in rows], dtype=torch.int64)
+
+
+def bytes_compare(col, other) -> torch.Tensor:
+    """Three-way compare per row, int8[n] of -1 / 0 / +1: ``col`` against a
+    second binary Column of the same length, or against one ``bytes`` value.
+
+    GPU: one thread per row, a word at a time where the two sides share their
+    alignment (csrc/bytes_order.hip). CPU: (a > b) - (a < b) over the rows.
+    """
+    _check_binary(col, "bytes_compare")
+    lit = None
+    if isinstance(other, (bytes, bytearray)):
+        lit = bytes(other)
+    else:
+        _check_binary(other, "bytes_compare")
+        if len(other) != len(col):
+            raise ValueError("bytes_compare: columns differ in row count")
+    if _use_native(col.data):
+        nat = require_native()
+        if lit is not None:
+            return nat.bytes_compare_lit(col.data.contiguous(),
+                                         col.offsets.contiguous(), lit)
+        if not other.data.is_cuda:
+            raise ValueError("bytes_compare: columns on different devices")
+        return nat.bytes_compare_cols(
+            col.data.contiguous(), col.offsets.contiguous(),
+            other.data.contiguous(), other.offsets.contiguous())
+    a = _bytes_rows(col)
+    b = [lit] * len(a) if lit is not None else _bytes_rows(other)
+    return torch.tensor([(x > y) - (x < y) for x, y in zip(a, b)],
+                        dtype=torch.int8)
+
+
 # --------------------------------------------------------------------- window
-_SCAN_OPS = {"sum": 0, "min": 1, "max": 2}
+_SCAN_OPS ={"sum": 0, "min": 1, "max": 2}
 _SCAN_IDENTITY = {"sum": 0.0, "min": float("inf"), "max": float("-inf")}
 _WINDOW_FUNCS = {"sum": 0, "count": 1, "avg": 2, "min": 3, "max": 4,
                  "first_value": 5, "last_value": 6, "count_star": 7}

@@ -323,20 +323,11 @@ class SqlExecutor:
                 key = v.data if isinstance(v, Column) and v.kind == "numeric" \
                     else v
                 if isinstance(key, Column):
-                    # binary sort key: CPU fallback
-                    import numpy as np
-                    vals = key.to_pylist()
-                    # NULLs (None) get a stable placeholder here; the
-                    # validity stable-sort below puts them in their
-                    # NULLS FIRST/LAST position
-                    idx = torch.tensor(
-                        sorted(range(len(vals)),
-                               key=lambda i: vals[i]
-                               if vals[i] is not None else b"",
-                               reverse=not asc),
-                        dtype=torch.int64, device=device)
-                else:
-                    idx = ops.sort_indices(key, ascending=asc)
+                    # binary sort key: its dense rank. NULLs share one
+                    # placeholder rank here; the validity stable-sort below
+                    # puts them in their NULLS FIRST/LAST position
+                    key = _string_order_key(key)
+                idx = ops.sort_indices(key, ascending=asc)
                 from .eval import expr_validity
                 kv = expr_validity(e, final_env)
                 if kv is not None and bool((~kv).any()):
@@ -434,16 +425,7 @@ class SqlExecutor:
                     e = ColumnRef(out_names[e.value - 1], None)
                 env = Env(dict(result.columns), result.num_rows, device)
                 v = eval_expr(e, env)
-                if isinstance(v, Column) and v.kind == "binary":
-                    vals = v.to_pylist()
-                    idx = torch.tensor(
-                        sorted(range(len(vals)),
-                               key=lambda i: vals[i]
-                               if vals[i] is not None else b"",
-                               reverse=not asc),
-                        dtype=torch.int64, device=device)
-                else:
-                    idx = ops.sort_indices(as_tensor(v, env), ascending=asc)
+                idx = ops.sort_indices(_order_key(v, env), ascending=asc)
                 from .eval import expr_validity
                 kv = expr_validity(e, env)
                 if isinstance(v, Column) and v.validity is not None:
@@ -473,8 +455,7 @@ class SqlExecutor:
         sort_keys = []
         for e, asc in reversed(w_.over.order_by):
             v = eval_expr(e, env)
-            key = v.data if isinstance(v, Column) and v.kind == "numeric" \
-                else as_tensor(v, env)
+            key = _order_key(v, env)
             sort_keys.append((key, asc))
             perm = perm[ops.sort_indices(key[perm], ascending=asc)]
         perm = perm[ops.sort_indices(gid[perm], ascending=True)]
@@ -549,8 +530,7 @@ class SqlExecutor:
         perm = torch.arange(n, dtype=torch.int64, device=device)
         for e, asc in reversed(w_.over.order_by):
             v = eval_expr(e, env)
-            key = v.data if isinstance(v, Column) and v.kind == "numeric" \
-                else as_tensor(v, env)
+            key = _order_key(v, env)
             perm = perm[ops.sort_indices(key[perm], ascending=asc)]
         perm = perm[ops.sort_indices(gid[perm], ascending=True)]
         out, ok = ops.window_frame(
@@ -624,8 +604,7 @@ class SqlExecutor:
         sort_keys = []
         for e, asc in reversed(w_.over.order_by):
             v = eval_expr(e, env)
-            key = v.data if isinstance(v, Column) and v.kind == "numeric" \
-                else as_tensor(v, env)
+            key = _order_key(v, env)
             sort_keys.append((key, asc))
             idx = ops.sort_indices(key[perm], ascending=asc)
             perm = perm[idx]
@@ -1048,24 +1027,10 @@ class SqlExecutor:
                 torch.ones(env.n_rows, device=device), gid, g, "count")
         if isinstance(arg, Column) and arg.kind == "binary" \
                 and name in ("min", "max"):
-            # lexicographic min/max over strings: host fallback (DataFusion
-            # supports string MIN/MAX; group counts are small post-hash)
-            pv = arg.to_pylist()
-            gl = gid.detach().to("cpu").tolist()
-            best = [None] * g
-            for v, gi in zip(pv, gl):
-                if v is None:
-                    continue
-                b = best[gi]
-                if b is None or (v < b if name == "min" else v > b):
-                    best[gi] = v
-            out = Column.from_bytes([b if b is not None else b""
-                                     for b in best])
-            if any(b is None for b in best):
-                out = Column(out.kind, out.data, out.offsets,
-                             torch.tensor([b is not None for b in best],
-                                          dtype=torch.bool, device=device))
-            return out
+            # lexicographic min/max over strings (DataFusion supports string
+            # MIN/MAX): reduce the dense rank per group over the valid rows,
+            # then gather one row that holds the winning rank
+            return _string_min_max(arg, gid, g, name)
         vals = as_tensor(arg, env)
         from .eval import expr_validity
         validity = expr_validity(a.args[0], env) if a.args else None
@@ -1133,6 +1098,50 @@ def _to_column(v, env: Env) -> Column:
         return v
     # scalar broadcast
     return Column("numeric", as_tensor(v, env))
+
+
+def _string_order_key(col: Column) -> torch.Tensor:
+    """Sortable stand-in for a binary key: its dense rank (ops.bytes_rank),
+    with every NULL row at -1."""
+    rank = ops.bytes_rank(col)
+    if col.validity is not None:
+        rank = torch.where(col.validity, rank, torch.full_like(rank, -1))
+    return rank
+
+
+def _order_key(v, env: Env) -> torch.Tensor:
+    """Sort key tensor of an evaluated ORDER BY expression."""
+    if isinstance(v, Column):
+        return v.data if v.kind == "numeric" else _string_order_key(v)
+    return as_tensor(v, env)
+
+
+def _string_min_max(arg: Column, gid: torch.Tensor, g: int, name: str
+                    ) -> Column:
+    """MIN / MAX of a binary column per group; a group with no valid row is
+    NULL, and the result carries validity only when some group is."""
+    n = len(arg)
+    device = gid.device
+    # ranks and row indices are below n: exact in f32 (the native segment
+    # reduction) under 2^24 rows, in f64 beyond
+    ft = torch.float32 if n < (1 << 24) else torch.float64
+    g32 = gid.to(torch.int32)
+    rank = ops.bytes_rank(arg).to(ft)
+    valid = arg.validity
+    if valid is not None:
+        fill = float("inf") if name == "min" else float("-inf")
+        rank = torch.where(valid, rank, torch.full_like(rank, fill))
+    best = ops.segment_reduce(rank, g32, g, name).to(ft)
+    wins = rank == best[gid.long()]
+    if valid is not None:
+        wins &= valid
+    ar = torch.arange(n, dtype=ft, device=device)
+    row = ops.segment_reduce(torch.where(wins, ar, torch.full_like(ar, n)),
+                             g32, g, "min").to(torch.int64)
+    has = row < n
+    out = arg.take(row.clamp(max=n - 1))
+    return Column(out.kind, out.data, out.offsets,
+                  None if bool(has.all()) else has)
 
 
 def _encode_keys(keys: list, device) -> Tuple[torch.Tensor, None, int]:

@@ -219,15 +219,40 @@ def _bin_eq_literal(col: Column, lit: bytes, device) -> torch.Tensor:
 
 
 def _bin_eq_col(a: Column, b: Column) -> torch.Tensor:
-    la = a.offsets[1:] - a.offsets[:-1]
-    lb = b.offsets[1:] - b.offsets[:-1]
-    mask = la == lb
-    if not bool(mask.any()):
-        return mask
-    # fallback per-row compare for candidates (vectorize later if hot)
-    av, bv = a.to_pylist(), b.to_pylist()
-    res = [x == y for x, y in zip(av, bv)]
-    return torch.tensor(res, dtype=torch.bool, device=a.data.device)
+    from .. import ops
+    return ops.bytes_compare(a, b) == 0
+
+
+_ORDER_TESTS = {"<": lambda c: c < 0, "<=": lambda c: c <= 0,
+                ">": lambda c: c > 0, ">=": lambda c: c >= 0}
+
+
+def _string_order_cmp(op: str, lv, rv, env: Env) -> torch.Tensor:
+    """`l OP r` for OP in < <= > >= where either side is a binary column or
+    a string literal: ops.bytes_compare, then a test of its sign. A NULL row
+    compares by the bytes it holds; the caller's validity pass drops it."""
+    from .. import ops
+    l_bin = isinstance(lv, Column) and lv.kind == "binary"
+    r_bin = isinstance(rv, Column) and rv.kind == "binary"
+
+    def lit(v):
+        if isinstance(v, str):
+            return v.encode()
+        if isinstance(v, (bytes, bytearray)):
+            return bytes(v)
+        raise SqlError("string compared with non-string")
+
+    if l_bin:
+        return _ORDER_TESTS[op](
+            ops.bytes_compare(lv, rv if r_bin else lit(rv)))
+    if r_bin:
+        # literal OP column: compare the other way round, mirror the test
+        mirror = {"<": ">", "<=": ">=", ">": "<", ">=": "<="}[op]
+        return _ORDER_TESTS[mirror](ops.bytes_compare(rv, lit(lv)))
+    a, b = lit(lv), lit(rv)
+    c = (a > b) - (a < b)
+    return torch.full((env.n_rows,), bool(_ORDER_TESTS[op](c)),
+                      dtype=torch.bool, device=env.device)
 
 
 def eval_expr(e, env: Env) -> Value:
@@ -310,10 +335,11 @@ def eval_expr(e, env: Env) -> Value:
             if not isinstance(lo_v, str) or not isinstance(hi_v, str):
                 raise SqlError("string BETWEEN needs string bounds")
             lob, hib = lo_v.encode(), hi_v.encode()
-            rows = ev.to_pylist()
-            r = torch.tensor([x is not None and lob <= x <= hib
-                              for x in rows], dtype=torch.bool,
-                             device=env.device)
+            from .. import ops
+            r = (ops.bytes_compare(ev, lob) >= 0) \
+                & (ops.bytes_compare(ev, hib) <= 0)
+            if ev.validity is not None:
+                r &= ev.validity  # a NULL row is not between anything
             return ~r if e.negated else r
         v = as_tensor(ev, env)
         lo = as_tensor(eval_expr(e.low, env), env)
@@ -425,15 +451,7 @@ def _eval_binop(e: BinaryOp, env: Env) -> Value:
         raise SqlError("|| requires strings")
     if l_bin or r_bin or isinstance(lv, str) or isinstance(rv, str):
         if e.op not in ("=", "!="):
-            # ordered string compare: CPU fallback
-            ls = lv.to_pylist() if l_bin else [
-                (lv.encode() if isinstance(lv, str) else lv)] * env.n_rows
-            rs = rv.to_pylist() if r_bin else [
-                (rv.encode() if isinstance(rv, str) else rv)] * env.n_rows
-            fn = {"<": lambda a, b: a < b, "<=": lambda a, b: a <= b,
-                  ">": lambda a, b: a > b, ">=": lambda a, b: a >= b}[e.op]
-            return torch.tensor([fn(a, b) for a, b in zip(ls, rs)],
-                                dtype=torch.bool, device=env.device)
+            return _string_order_cmp(e.op, lv, rv, env)
         if l_bin and isinstance(rv, str):
             r = _bin_eq_literal(lv, rv.encode(), env.device)
         elif r_bin and isinstance(lv, str):

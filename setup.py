@@ -20,7 +20,7 @@ sources = [
     os.path.join(CSRC, f)
     for f in ("bindings.cpp", "filter.hip", "hash_agg.hip", "hash_join.hip",
               "gemm_bf16.hip", "gemm_8phase.hip", "rowops.hip", "attention.hip", "proto_decode.hip", "proto_encode.hip", "radix_sort.hip", "json_decode.hip",
-              "stepfused.hip", "window.hip")
+              "stepfused.hip", "window.hip", "bytes_order.hip")
 ]
 
 setup(
